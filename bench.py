@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- benchmark of the MI355X-native ipcr primer scan.  Prints ONE JSON line on rank 0.
 
-    python bench.py                          # 1 GPU, workload C2 (the headline), other workloads in config.other_workloads
+    python bench.py                          # 1 GPU, workload C2 (the headline) only: set-up, warm-up, the timed steps
+    python bench.py --full                   # ... and everything else: other workloads in config.other_workloads,
+                                             # cpu_baseline, panel compile times, HBM traffic, repeated short windows
     python bench.py --gpus 8                 # starts 8 ranks itself (torch.distributed.run as a child process)
     python bench.py --workload c4            # the 1024-row multiplex panel as the main line
+    python bench.py --dump-outputs DIR       # also writes the last timed step's products to DIR/*.npy
 
 Workloads (BASELINE.json configs[1..4]; synthetic 3.0 Gb genome per GPU = 24 records x 125 Mb
 of the reference's benchDNA LCG, resident in HBM as 2-bit + invalid-bit tiles when the timed region starts):
@@ -344,7 +347,7 @@ def run_workload(ctx, name, steps, warmup):
     # own, performance_benchmark_test.go:108-153) + the first scan, which builds the panel's kernel with hiprtc -- COLD: the
     # code-object cache directory is empty for this source; WARM: another panel object of the same source, the code object
     # read back from the disk cache (what a second `ipcr` run with the same primers pays)
-    compile_times = panel_compile_times(ctx, eng, spec, genome) if name not in ctx.compile_done else None
+    compile_times = panel_compile_times(ctx, eng, spec, genome) if ctx.args.full and name not in ctx.compile_done else None
     ctx.compile_done.add(name)
     cp = eng.CompilePanel(spec["pairs"])
     # three scratches in rotation: one being swept, one being joined on the host, one whose hit buffer the
@@ -415,12 +418,14 @@ def run_workload(ctx, name, steps, warmup):
             tdist.barrier()
         return time.perf_counter() - t0, fms, n
 
-    # A window of few short passes (the driver's 20 x 0.19 ms = 4 ms) is thin evidence: such a window is repeated -- every
-    # repetition again exactly `steps` passes, bracketed the same way -- and the MEDIAN window is reported (all of them
-    # in window_ms_min / max).  Long windows (>= 50 ms) stand alone.
+    # The headline (ms_per_step, value) is ONE window of exactly `steps` passes, the last one timed: its last pass is the
+    # one verified (and dumped).  A window of few short passes (the driver's 20 x 0.19 ms = 4 ms) is thin evidence: with
+    # --full such a window is timed 25 times in a row -- every window exactly `steps` passes, bracketed the same way --
+    # the headline is the last of them, and the spread of all is reported (window_ms_min / median / max).  Long windows
+    # (>= 50 ms) stand alone.
     el0, filter_ms, nprod = timed_window()
     windows = [el0]
-    if el0 < 0.05 and not os.environ.get("IPCR_BENCH_ONE_WINDOW"):
+    if ctx.args.full and el0 < 0.05 and not os.environ.get("IPCR_BENCH_ONE_WINDOW"):
         while len(windows) < 25:
             el, fms, n = timed_window()
             windows.append(el)
@@ -433,7 +438,7 @@ def run_workload(ctx, name, steps, warmup):
         ptot = torch.tensor([nprod], dtype=torch.int64, device=ctx.cdev)
         tdist.all_reduce(ptot, op=tdist.ReduceOp.SUM)
         nprod = int(ptot.item())
-    elapsed = sorted(windows)[len(windows) // 2]
+    elapsed = windows[-1]
     last = scs[(steps - 1) % len(scs)]   # scratch holding the last pass
     # ---- correctness outside the timed region ----
     if not multi:
@@ -470,8 +475,10 @@ def run_workload(ctx, name, steps, warmup):
         native_exchange=bool(xchg.native) if multi else None, native_exchange_verified=xchg.native_verified if multi else None,
         compile_times=compile_times,
         windows=len(windows), window_ms_min=min(windows) * 1e3, window_ms_max=max(windows) * 1e3,
+        window_ms_median=sorted(windows)[len(windows) // 2] * 1e3,
         probe_ms=(sum(probe_ms[-steps:]) / max(1, len(probe_ms[-steps:]))) if probe_ms else None,
-        prods=prods)
+        prods=prods, pair_ids=[p.ID for p in spec["pairs"]],
+        probe_hits=[(h.found, h.strand, h.pos, h.mm) for h in probe_out[:len(prods)]] if probe and not multi else None)
     for s_ in scs:
         s_.close()
     if host_sc is not None:
@@ -810,6 +817,46 @@ def cpu_baseline_bounded(ctx, name, seconds: float = 3.0):
     return cpu_baseline(name, spec, host0, seconds, gpu_n, sample_bases=n, chunk_bases=chunk or 4_000_000)
 
 
+# ----------------------------------------------------------------------------------------------- outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, res):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float64 / float32 .npy files, so that two builds
+    can be compared output for output (the inputs depend on the arguments only):
+      products.npy                    (n, 8) float64: record, start, end, length, pair (index into the workload's pair
+                                      list), type (0 forward, 1 revcomp), forward mismatches, reverse mismatches
+      products_fwd_mismatch_idx.npy   (n, 16) float32: the forward primer's mismatch positions, -1 where there is none
+      products_rev_mismatch_idx.npy   (n, 16) float32: the same for the reverse primer
+      probe_hits.npy                  (n, 4) float64, C5 on one GPU: found, strand (ASCII code), position, mismatches
+      products_rows.npy               only if n products exceed 64 MB in all: the rows kept, a fixed sample (seed 0)
+    With several GPUs the products are rank 0's join of the whole job's hit records."""
+    import numpy as np
+    prods, pair_index = res["prods"], {pid: i for i, pid in enumerate(res["pair_ids"])}
+    n = len(prods)
+    per_row = 8 * 8 + 2 * 16 * 4 + (4 * 8 if res["probe_hits"] is not None else 0)
+    rows = np.arange(n)
+    if n * per_row > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // per_row, replace=False))
+    prod = np.empty((len(rows), 8), dtype=np.float64)
+    fidx = np.full((len(rows), 16), -1, dtype=np.float32)
+    ridx = np.full((len(rows), 16), -1, dtype=np.float32)
+    for j, i in enumerate(rows):
+        p = prods[i]
+        prod[j] = (p.Record, p.Start, p.End, p.Length, pair_index[p.ExperimentID], 0 if p.Type == "forward" else 1,
+                   p.FwdMM, p.RevMM)
+        fidx[j, :len(p.FwdMismatchIdx)] = p.FwdMismatchIdx
+        ridx[j, :len(p.RevMismatchIdx)] = p.RevMismatchIdx
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "products.npy"), prod)
+    np.save(os.path.join(dirname, "products_fwd_mismatch_idx.npy"), fidx)
+    np.save(os.path.join(dirname, "products_rev_mismatch_idx.npy"), ridx)
+    if res["probe_hits"] is not None:
+        np.save(os.path.join(dirname, "probe_hits.npy"), np.asarray(res["probe_hits"], dtype=np.float64).reshape(-1, 4)[rows])
+    if len(rows) < n:
+        np.save(os.path.join(dirname, "products_rows.npy"), rows.astype(np.float64))
+
+
 # ----------------------------------------------------------------------------------------------- main
 def main() -> None:
     # HIP maps streams onto a few hardware queues (4 by default), in creation order.  This job has a dozen (three
@@ -831,6 +878,12 @@ def main() -> None:
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo to rehearse)")
     ap.add_argument("--no-pipeline", action="store_true", help="finish every pass before the next one is enqueued")
     ap.add_argument("--no-traffic", action="store_true", help="do not measure roofline.traffic with rocprofv3 --pmc children (quote profiles/ instead)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: config.other_workloads, cpu_baseline, panel compile times, roofline.traffic "
+                         "measured by rocprofv3 --pmc children, short timed windows repeated (--no-others, "
+                         "--no-cpu-baseline and --no-traffic leave their parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (its products) to DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 40 if args.workload in ("c4", "c4n") else 2000
@@ -844,7 +897,7 @@ def main() -> None:
 
     chunk_rates, c5_chunk, all_dev_rates, traffic, chunk_panel = None, None, None, None, None
     single = "RANK" not in os.environ and args.gpus <= 1 and not os.environ.get("IPCR_EXCHANGE_SELFTEST")
-    if not args.no_others and single:
+    if args.full and not args.no_others and single:
         chunk_rates = scan_chunk_rates(args)      # child process, before anything here has initialised HIP
         c5_chunk = scan_chunk_rates(args, probe=True)
         # the drop-in call under C4's panel (1024 rows: seed-index kernel), 16 workers: clean chunks and chunks that hold N
@@ -854,9 +907,9 @@ def main() -> None:
             chunk_panel["gbases_per_s_" + key] = cr["gbases_per_s_16_workers"]
             chunk_panel["calls_unwindowed_" + key] = cr["calls_unwindowed_16_workers"]
     under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if not args.no_traffic and not under_profiler and single and args.records == RECORDS and args.record_len == RECORD_LEN:
+    if args.full and not args.no_traffic and not under_profiler and single and args.records == RECORDS and args.record_len == RECORD_LEN:
         traffic = measure_traffic(args.workload, "ipcr_index_filter" if args.workload in ("c4", "c4n") else "ipcr_filter")
-    if not args.no_others and os.environ.get("RANK") == "0" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if args.full and not args.no_others and os.environ.get("RANK") == "0" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         all_dev_rates = scan_chunk_all_devices(int(os.environ["WORLD_SIZE"]), args)
 
     import glob
@@ -880,14 +933,16 @@ def main() -> None:
     ctx.multi = world > 1 or bool(os.environ.get("IPCR_EXCHANGE_SELFTEST"))  # selftest: one rank runs the RCCL exchange too
     ctx.revcomp = primer.RevComp
     ctx.genomes = {}
-    ctx.want_cpu = (not args.no_cpu_baseline) and rank == 0 and world == 1 and args.workload in ("c2", "c3", "c4")
-    ctx.want_cpu_others = (not args.no_cpu_baseline) and (not args.no_others) and rank == 0 and world == 1 and not ctx.multi
+    ctx.want_cpu = args.full and (not args.no_cpu_baseline) and rank == 0 and world == 1 and args.workload in ("c2", "c3", "c4")
+    ctx.want_cpu_others = args.full and (not args.no_cpu_baseline) and (not args.no_others) and rank == 0 and world == 1 and not ctx.multi
     ctx.compile_done = set()
 
     res = run_workload(ctx, args.workload, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     others = {}
-    if not args.no_others:
+    if args.full and not args.no_others:
         if world == 1 and not ctx.multi:
             for nm, st, wu in (("c2n", 400, 100), ("c3", 400, 100), ("c4", 30, 5), ("c4n", 20, 3), ("c5", 300, 50)):
                 if nm == args.workload:
@@ -936,8 +991,9 @@ def main() -> None:
         "warmup": args.warmup,
         "warmup_actual": res["warmup_actual"],
         "ms_per_step": round(res["ms_per_step"], 4),
-        "windows": res["windows"],                      # timed windows of `steps` passes each; ms_per_step / value are the median window's
+        "windows": res["windows"],                      # timed windows of `steps` passes each (--full: 25 if short); ms_per_step / value are the last window's
         "window_ms_min": round(res["window_ms_min"], 4),
+        "window_ms_median": round(res["window_ms_median"], 4),
         "window_ms_max": round(res["window_ms_max"], 4),
         "higher_is_better": True,
         "scaling": "weak",

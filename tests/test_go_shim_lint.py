@@ -3,9 +3,10 @@ image has no Go toolchain -- so it is linted against the C header it binds: ever
 include/ipcr_hip.h with that many parameters, every C.IPCR_* constant and C.ipcr_* type exists, every struct field it
 names is a field of that struct (cgo spells a field called like a Go keyword with a leading underscore: `_type`).
 The test fails when the header drifts away from the shim, or the shim from the header."""
+import hashlib
+import json
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
@@ -167,13 +168,55 @@ def test_go_shim_implements_the_pipeline_interfaces():
     assert re.search(r"func \(v Visitor\) Visit\(p engine\.Product\) \(bool, probeoutput\.AnnotatedProduct, error\)", prb)
 
 
+def parse_patch(text):
+    """-> {path: [{"old_start", "old_len", "new_len", "old": [lines], "new": [lines]}]} of a unified diff"""
+    files, hunks, h = {}, None, None
+    for ln in text.splitlines():
+        m = re.match(r"--- a/(\S+)", ln)
+        if m:
+            hunks = files.setdefault(m.group(1), [])
+            h = None
+            continue
+        if ln.startswith("+++ ") and h is None:
+            continue
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+\d+(?:,(\d+))? @@", ln)
+        if m and hunks is not None:
+            h = {"old_start": int(m.group(1)), "old_len": int(m.group(2) or "1"), "new_len": int(m.group(3) or "1"),
+                 "old": [], "new": []}
+            hunks.append(h)
+            continue
+        if h is None or len(h["old"]) == h["old_len"] and len(h["new"]) == h["new_len"]:
+            h = None
+            continue
+        tag, body = (ln[:1], ln[1:]) if ln else (" ", "")
+        if tag in " -":
+            h["old"].append(body)
+        if tag in " +":
+            h["new"].append(body)
+    return files
+
+
 def test_patch_applies_to_the_reference(tmp_path):
-    ref = "/root/reference"
-    if not os.path.isdir(ref) or shutil.which("patch") is None:
-        pytest.skip("no reference checkout / no patch(1) here")
-    for rel in ("internal/appcore/core.go", "internal/probeapp/app.go"):
+    """the patch applies to the reference's internal/appcore/core.go and internal/probeapp/app.go without fuzz or offset:
+    every hunk's pre-image (its context and removed lines) is what the reference holds at that position -- the hunks'
+    positions and the SHA-256 of those lines were recorded from the reference by tests/golden/make_patch_base.py -- and
+    patch(1) applies the patch (dry run) to files that hold these pre-images at these positions"""
+    base = json.load(open(os.path.join(ROOT, "tests", "golden", "appcore_patch_base.json")))
+    files = parse_patch(open(os.path.join(GO_DIR, "appcore_core.patch")).read())
+    assert set(files) == set(base["files"]) == {"internal/appcore/core.go", "internal/probeapp/app.go"}
+    for rel, hunks in files.items():
+        rec = base["files"][rel]
+        assert [(h["old_start"], h["old_len"]) for h in hunks] == [(r["old_start"], r["old_len"]) for r in rec["hunks"]], rel
+        lines = ["// line %d of the reference's %s (not recorded)" % (i + 1, rel) for i in range(rec["lines"])]
+        for h, r in zip(hunks, rec["hunks"]):
+            assert (len(h["old"]), len(h["new"])) == (h["old_len"], h["new_len"]), (rel, h["old_start"])
+            got = hashlib.sha256("\n".join(h["old"]).encode()).hexdigest()
+            assert got == r["sha256"], f"{rel}: the hunk at line {h['old_start']} no longer matches the reference"
+            lines[h["old_start"] - 1:h["old_start"] - 1 + h["old_len"]] = h["old"]
+        assert len(lines) == rec["lines"], rel
         os.makedirs(os.path.dirname(tmp_path / rel), exist_ok=True)
-        shutil.copy(os.path.join(ref, rel), tmp_path / rel)
+        (tmp_path / rel).write_text("\n".join(lines) + "\n")
     r = subprocess.run(["patch", "-p1", "--dry-run", "-i", os.path.join(GO_DIR, "appcore_core.patch")], cwd=tmp_path,
                        capture_output=True, text=True)
-    assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout, r.stdout + r.stderr
+    assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout and "offset" not in r.stdout, \
+        r.stdout + r.stderr

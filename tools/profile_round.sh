@@ -13,11 +13,11 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 export IPCR_JIT_ASYNC=0   # every pass on the panel's own kernels, from the first one
 if [ $stage != prof ]; then
-python3 bench.py > "$out/bench.json" 2> "$out/bench.err" || { tail -5 "$out/bench.err"; exit 1; }
+python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err" || { tail -5 "$out/bench.err"; exit 1; }
 tail -c 600 "$out/bench.json"; echo
 python3 bench.py --no-pipeline --no-cpu-baseline --no-others --no-traffic > "$out/bench_serial.json" 2> "$out/bench_serial.err" || exit 1
 for w in c3 c4; do
-  python3 bench.py --workload $w --no-others > "$out/bench_$w.json" 2> "$out/bench_$w.err" || { tail -5 "$out/bench_$w.err"; exit 1; }
+  python3 bench.py --workload $w --full --no-others > "$out/bench_$w.json" 2> "$out/bench_$w.err" || { tail -5 "$out/bench_$w.err"; exit 1; }
 done
 fi
 [ $stage = bench ] && { echo done; exit 0; }
