@@ -1544,6 +1544,7 @@ ipcr_status ipcr_genome_add_record(ipcr_genome *g, const uint8_t *seq, uint64_t 
     if (len + 16 > g->staging_cap) {
         if (g->staging) (void)hipFree(g->staging);
         g->staging = nullptr;
+        g->staging_fine = false; // coarse-grained: the next host-packed record re-allocates it before writing through the BAR
         g->staging_cap = len + 16 + (len >> 3);
         HIPCHK(hipMalloc((void **)&g->staging, g->staging_cap));
     }
@@ -3332,6 +3333,7 @@ ipcr_status ipcr_scan_chunk(const ipcr_panel *p, ipcr_scratch *s, const uint8_t 
     if (len + 16 > g->staging_cap) {
         if (g->staging) (void)hipFree(g->staging);
         g->staging = nullptr;
+        g->staging_fine = false; // coarse-grained: the next host-packed record re-allocates it before writing through the BAR
         g->staging_cap = len + 16 + (len >> 3);
         HIPCHK(hipMalloc((void **)&g->staging, g->staging_cap));
     }

@@ -838,3 +838,87 @@ def test_null_stream_fills_are_waited_for():
                 assert "hipStreamSynchronize(nullptr)" in window or "hipDeviceSynchronize()" in window, \
                     "%s:%d: hipMemset on the null stream is not waited for before the library's non-blocking streams go on" % (os.path.basename(path), i + 1)
     assert seen >= 3
+
+
+def test_plain_staging_allocations_clear_the_fine_grained_flag():
+    """A genome's staging buffer is fine-grained (hipExtMallocWithFlags) when the host packer writes it through the PCIe BAR, and
+    staging_fine says so; the ASCII paths (ipcr_genome_add_record, ipcr_scan_chunk) re-allocate it with plain hipMalloc.  Such a
+    re-allocation must clear staging_fine between the hipFree of the old buffer and the hipMalloc of the new one: otherwise the next
+    host-packed record (4096 bases, then 4090, then 4096 again) writes its planes through the BAR into coarse-grained memory."""
+    import glob
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    seen = 0
+    for path in sorted(glob.glob(os.path.join(root, "ipcr_amd", "csrc", "*.cpp"))):
+        lines = open(path).read().split("\n")
+        for i, line in enumerate(lines):
+            if not re.search(r"\bhipMalloc\s*\(\s*\(void\s*\*\*\)\s*&\s*g->staging\s*,", line):
+                continue
+            seen += 1
+            free = max((j for j in range(max(0, i - 16), i) if "hipFree(g->staging)" in lines[j]), default=None)
+            where = "%s:%d" % (os.path.basename(path), i + 1)
+            assert free is not None, "%s: g->staging allocated without freeing the old buffer just before" % where
+            between = "\n".join(lines[free:i])
+            assert re.search(r"g->staging_fine\s*=\s*false\s*;", between), \
+                "%s: plain hipMalloc of g->staging leaves staging_fine as it was" % where
+    assert seen >= 3
+
+
+def _brute_matches(seq, pat, k, left, tw_dev):
+    """the match rule stated base by base: at every position the j with not base_match(seq[pos + j], pat[j]); a hit has at
+    most k of them and none inside the enforced window (the first tw_dev bases of a left-window pattern, the last tw_dev of
+    a right-window one)"""
+    L = len(pat)
+    win = set(range(tw_dev)) if left else set(range(L - tw_dev, L))
+    out = []
+    for pos in range(len(seq) - L + 1):
+        idx = []
+        for j in range(L):
+            if not O.base_match(chr(seq[pos + j]), pat[j]):
+                idx.append(j)
+                if len(idx) > k or j in win:
+                    break
+        else:
+            out.append((pos, tuple(idx)))
+    return out
+
+
+@pytest.mark.parametrize("k,tw,seed_len", [(0, 5, 12), (1, 0, 0), (2, 3, 12), (3, 5, 0)])
+def test_hit_oracle_equals_the_brute_force_rule(k, tw, seed_len):
+    """the expected hit lists of tests/test_gpu_hits.py rest on synth_hits (the oracle's find_matches + the device window
+    rule): both against a third, base-by-base statement of the rule, on that file's own planted records (exhaustive and
+    structured mismatch sets, junk bytes, the seed-span reset flag), on records cut through a site (overhangs) and on
+    random sequence with N, lower case and IUPAC letters in the genome"""
+    import test_gpu_hits as G
+    rng = random.Random(60 + k)
+    pairs = [primer.Pair("a", rand_primer(rng, 16, 20, amb=True), rand_primer(rng, 18, 24, amb=False), 0, 0),
+             primer.Pair("b", rand_primer(rng, 8, 12, amb=True), rand_primer(rng, 30, 40, amb=True), 0, 0)]
+    cp = engine.New(engine.Config(MaxMM=k, TerminalWindow=tw, SeedLen=seed_len)).CompilePanel(pairs)
+    checked = 0
+    for dirty in (False, True):
+        mode = 1 if (dirty and G.modes_differ(cp)) else 0
+        seqs, _ = G.records_with_sites(rng, cp, mode, k, dirty, exhaustive_max_len=16 if k <= 2 else 0, nrec=2)
+        seqs = [s[:6000] for s in seqs]
+        seqs += [s[:n] for s in seqs for n in (37, 101)]                     # cut through sites: overhangs
+        junk = list(rand_seq(rng, 1500, junk=True))
+        for _ in range(40):
+            junk[rng.randrange(1500)] = rng.choice("RYSWKMBDHVNnacgtx-")
+        seqs.append("".join(junk).encode())
+        for r, seq in enumerate(seqs):
+            rows = synth_hits(cp, seq, k, r, mode)
+            by_pat = {}
+            for h in rows:
+                by_pat.setdefault(int(h["pattern"]) & 0x7FFFFFFF, []).append(h)
+            for gid in cp.scanned_patterns(mode):
+                pat, left, tw_dev, soff, slen = cp.pattern_info(gid)
+                want = _brute_matches(seq, pat, k, left, tw_dev)
+                if left:
+                    ms = [m for m in O.find_matches(seq, pat, k, 0, 0) if all(j >= tw_dev for j in m.idx)]
+                else:
+                    ms = O.find_matches(seq, pat, k, 0, tw_dev)
+                assert [(m.pos, tuple(m.idx)) for m in ms] == want, (pat, left, tw_dev)
+                got = sorted((int(h["pos"]), int(h["mm0"]) | int(h["mm1"]) << 64, int(h["pattern"]) >> 31) for h in by_pat.get(gid, []))
+                flag = lambda p: int(bool(slen) and any(c not in b"ACGTacgt" for c in seq[p + soff:p + soff + slen]))
+                assert got == [(p, sum(1 << j for j in idx), flag(p)) for p, idx in want], (pat, left, tw_dev)
+                checked += len(want)
+    assert checked >= 50
+    cp.close()
