@@ -1084,6 +1084,7 @@ struct ipcr_genome {
     uint32_t *d_flags = nullptr; // per record, bit0 = holds a non-ACGTacgt byte
     uint64_t *d_rec_start = nullptr, *d_rec_len = nullptr;
     uint32_t *d_block_rec = nullptr; // per block: last record that starts at or before the block (verify's first guess)
+    uint64_t *d_colmask = nullptr;   // per block, bit lane: column 64 block + lane holds an inv bit (kernels.hip: ipcr_colmask_set)
     std::vector<uint32_t> block_rec;
     std::vector<uint64_t> rec_start, rec_len; // padded start, length
     std::vector<std::string> ids;             // record IDs (FASTA loader; empty for records added as bytes)
@@ -1121,7 +1122,9 @@ ipcr_status genome_alloc(ipcr_genome *g, uint64_t cap_cols, uint32_t max_records
     HIPCHK(hipMalloc((void **)&g->d_rec_start, (uint64_t)max_records * 8ull));
     HIPCHK(hipMalloc((void **)&g->d_block_rec, (blocks + 1) * 4ull));
     HIPCHK(hipMalloc((void **)&g->d_rec_len, (uint64_t)max_records * 8ull));
+    HIPCHK(hipMalloc((void **)&g->d_colmask, (blocks + 1) * 8ull));
     HIPCHK(hipMemset(g->d_flags, 0, (uint64_t)max_records * 4ull));
+    HIPCHK(hipMemset(g->d_colmask, 0xFF, (blocks + 1) * 8ull)); // every column dirty until a tile writer says otherwise
     HIPCHK(hipStreamSynchronize(nullptr)); // (the fill runs on the null stream; the genome's stream is non-blocking and must not overtake it)
     return IPCR_OK;
 }
@@ -1134,6 +1137,8 @@ void genome_free_buffers(ipcr_genome *g) {
     if (g->d_block_rec) (void)hipFree(g->d_block_rec);
     g->d_block_rec = nullptr;
     if (g->d_rec_len) (void)hipFree(g->d_rec_len);
+    if (g->d_colmask) (void)hipFree(g->d_colmask);
+    g->d_colmask = nullptr;
     g->planes = g->rst = g->d_flags = nullptr;
     g->d_rec_start = g->d_rec_len = nullptr;
 }
@@ -1172,8 +1177,8 @@ ipcr_status genome_add_device(ipcr_genome *g, const uint8_t *dseq, uint64_t len,
                     (unsigned long long)g->next_col, (unsigned long long)cols, (unsigned long long)g->cap_cols);
     if ((reinterpret_cast<uintptr_t>(dseq) & 15u) != 0) return fail(IPCR_ERR_INVALID, "device sequence pointer must be 16-byte aligned");
     const uint32_t rec = (uint32_t)g->rec_start.size();
-    if (ext_flag) HIPCHK(ipcr::launch_pack(g->stream, dseq, len, g->next_col, cols, g->planes, g->rst, ext_flag, g->d_rec_start + rec, g->d_rec_len + rec, g->e0, g->e1));
-    else HIPCHK(ipcr::launch_pack(g->stream, dseq, len, g->next_col, cols, g->planes, g->rst, g->d_flags + rec, nullptr, nullptr, g->e0, g->e1));
+    if (ext_flag) HIPCHK(ipcr::launch_pack(g->stream, dseq, len, g->next_col, cols, g->planes, g->rst, g->d_colmask, ext_flag, g->d_rec_start + rec, g->d_rec_len + rec, g->e0, g->e1));
+    else HIPCHK(ipcr::launch_pack(g->stream, dseq, len, g->next_col, cols, g->planes, g->rst, g->d_colmask, g->d_flags + rec, nullptr, nullptr, g->e0, g->e1));
     if (wait) {
         HIPCHK(hipEventSynchronize(g->e1));
         float ms = 0;
@@ -1207,7 +1212,7 @@ ipcr_status genome_add_device_batch(ipcr_genome *g, const uint8_t *dbase, const 
     uint32_t *d_prefix = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_tmp) + ((n * sizeof(ipcr_pack_rec) + 15) & ~(size_t)15));
     HIPCHK(hipMemcpyAsync(d_recs, recs.data(), n * sizeof(ipcr_pack_rec), hipMemcpyHostToDevice, g->stream));
     HIPCHK(hipMemcpyAsync(d_prefix, prefix.data(), (n + 1) * 4, hipMemcpyHostToDevice, g->stream));
-    HIPCHK(ipcr::launch_pack_batch(g->stream, dbase, d_recs, d_prefix, (uint32_t)n, prefix[n], g->planes, g->rst, g->d_flags));
+    HIPCHK(ipcr::launch_pack_batch(g->stream, dbase, d_recs, d_prefix, (uint32_t)n, prefix[n], g->planes, g->rst, g->d_colmask, g->d_flags));
     HIPCHK(hipStreamSynchronize(g->stream)); // recs / prefix are host vectors of this call
     for (size_t i = 0; i < n; ++i) {
         g->rec_start.push_back(recs[i].col0 * IPCR_COLUMN_BASES);
@@ -1229,13 +1234,13 @@ ipcr_status genome_pad(ipcr_genome *g) {
     const uint64_t need = (g->next_col + 63) / 64 * 64 + 64;
     const uint64_t lo = g->next_col; // first column that must be padding; known padding: [max(lo, stale_until), padded_until)
     if (g->stale_until > lo) {       // bases of a forgotten, longer record follow the last one (a reused chunk genome)
-        HIPCHK(ipcr::launch_fill_pad(g->stream, g->planes, g->rst, lo, std::min(g->stale_until, need)));
+        HIPCHK(ipcr::launch_fill_pad(g->stream, g->planes, g->rst, g->d_colmask, lo, std::min(g->stale_until, need)));
         if (g->stale_until > need) return IPCR_OK; // [lo, need) is padding now; what lies beyond stays marked stale
         g->padded_until = std::max(g->padded_until, g->stale_until);
         g->stale_until = lo;
     }
     if (g->padded_until < need) {
-        HIPCHK(ipcr::launch_fill_pad(g->stream, g->planes, g->rst, std::max(lo, g->padded_until), need));
+        HIPCHK(ipcr::launch_fill_pad(g->stream, g->planes, g->rst, g->d_colmask, std::max(lo, g->padded_until), need));
         g->padded_until = need;
     }
     return IPCR_OK;
@@ -1385,7 +1390,7 @@ static bool genome_add_host_packed(ipcr_genome *g, const uint8_t *seq, uint64_t 
         if (need_inv) bar_copy(g->staging + W * 8u, g->h_planes, W * 4u * (lower ? 2u : 1u)); // (through the BAR as well: no copy operation)
         bar_flush(bi);
         if (!hip(ipcr::launch_tiles_from_linear(g->stream, dlo, dlo + W, need_inv ? dlo + 2 * W : nullptr, lower ? dlo + 3 * W : nullptr, col0, col0 + c0, nc, len,
-                                                g->planes, g->rst, nullptr, nullptr, c0 == 0 ? g->e0 : nullptr, c0 + nc >= cols ? g->e1 : nullptr), "tiles_from_linear")) break;
+                                                g->planes, g->rst, g->d_colmask, nullptr, nullptr, c0 == 0 ? g->e0 : nullptr, c0 + nc >= cols ? g->e1 : nullptr), "tiles_from_linear")) break;
         if (c0 + nc < cols && !hip(hipStreamSynchronize(g->stream), "hipStreamSynchronize")) break; // the next group reuses both buffers
     }
     if (*st != IPCR_OK) { (void)hipStreamSynchronize(g->stream); return true; }
@@ -1510,7 +1515,7 @@ ipcr_status ipcr_internal_genome_add_fasta_hostpacked(ipcr_genome *g, const char
                        *iv32 = reinterpret_cast<const uint32_t *>(fs.d_iv + word0[r]);
         const uint32_t any = rec_dirty[r];
         HIPCHK(ipcr::launch_tiles_from_linear(g->stream, lo32, hi32, any ? iv32 : nullptr, nullptr, col0, col0, cols[r], fr.len,
-                                              g->planes, g->rst, nullptr, nullptr, nullptr, nullptr, any ? fs.d_bits + bit0[r] : nullptr));
+                                              g->planes, g->rst, g->d_colmask, nullptr, nullptr, nullptr, nullptr, any ? fs.d_bits + bit0[r] : nullptr));
         const uint32_t rec = (uint32_t)g->rec_start.size();
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(g->d_flags + rec), (int)any, 1, g->stream));
         genome_account_record(g, fr.len, cols[r]);
@@ -1821,6 +1826,18 @@ extern "C" int32_t ipcr_internal_device_bar(int32_t slot) {
     return !bi.writable || !env_flag("IPCR_CHUNK_BAR", true) ? 0 : (bi.hdp_flush ? 2 : 1);
 }
 
+// tests: the column mask of a genome, words [0, nwords) (one per block) -> out; returns the words the genome has
+extern "C" int64_t ipcr_internal_genome_column_mask(ipcr_genome *g, uint64_t *out, uint64_t nwords) {
+    if (!g || !g->d_colmask) return -1;
+    const uint64_t have = g->cap_cols / 64 + 2;
+    if (out && nwords) {
+        DeviceGuard dg(g->device);
+        if (hipStreamSynchronize(g->stream) != hipSuccess) return -1;
+        if (hipMemcpy(out, g->d_colmask, std::min(nwords, have) * 8ull, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    }
+    return (int64_t)have;
+}
+
 // fasta.cpp: its file reads run on the same threads (threads started per slab slowed the slab copies, see there)
 void ipcr_internal_pool_run(size_t n, const std::function<void(size_t)> &fn, int phys) { PackPool::get().run(n, [&](size_t i) { fn(i); }, phys); }
 bool ipcr_internal_bind_thread(int phys) { return bind_this_thread(phys); }
@@ -2081,7 +2098,7 @@ ipcr_status scan_launch(const ipcr_panel *p, ipcr_scratch *s, ipcr_genome *g) {
                 }();
                 v.withhold = withhold > 0 ? (uint32_t)withhold : 0u;
             }
-            HIPCHK(ipcr::jit_launch(jit[gi], lane, g->planes, block0, nblocks, s->d_queue, s->qcap, qc, v,
+            HIPCHK(ipcr::jit_launch(jit[gi], lane, g->planes, g->d_colmask, block0, nblocks, s->d_queue, s->qcap, qc, v,
                                     gi == 0 ? s->ev[0] : nullptr, gi + 1 == jit.size() ? s->ev[1] : nullptr));
         }
         s->stats.kernel_kind = 1;
@@ -2136,7 +2153,7 @@ ipcr_status scan_launch(const ipcr_panel *p, ipcr_scratch *s, ipcr_genome *g) {
             v.hcap = s->hcap;
             v.counts = cnt;
             for (size_t gi = 0; gi < sd.leftover_jit.size(); ++gi)
-                HIPCHK(ipcr::jit_launch(sd.leftover_jit[gi], lane, g->planes, block0, nblocks, s->d_queue, s->qcap, qc, v, nullptr,
+                HIPCHK(ipcr::jit_launch(sd.leftover_jit[gi], lane, g->planes, g->d_colmask, block0, nblocks, s->d_queue, s->qcap, qc, v, nullptr,
                                         gi + 1 == sd.leftover_jit.size() ? s->ev[1] : nullptr));
         } else if (more)
             HIPCHK(ipcr::launch_filter_generic(lane, g->planes, block0, nblocks, sd.dev, (uint32_t)ix.leftover.size(),
@@ -3244,7 +3261,7 @@ ipcr_status ipcr_scan_chunk(const ipcr_panel *p, ipcr_scratch *s, const uint8_t 
             } else if (!zerocopy) HIPCHK(hipMemcpyAsync(d, slab, W * 4u * (lower ? 4u : need_inv ? 3u : 2u), hipMemcpyHostToDevice, g->stream));
             const uint32_t *dl = zerocopy ? reinterpret_cast<const uint32_t *>(slab) : reinterpret_cast<const uint32_t *>(d);
             HIPCHK(ipcr::launch_tiles_from_linear(g->stream, dl, dl + W, need_inv ? dl + 2 * W : nullptr, lower ? dl + 3 * W : nullptr, col0, col0 + c0, nc, len,
-                                                  g->planes, g->rst, i == 0 ? g->d_rec_start : nullptr, i == 0 ? g->d_rec_len : nullptr,
+                                                  g->planes, g->rst, g->d_colmask, i == 0 ? g->d_rec_start : nullptr, i == 0 ? g->d_rec_len : nullptr,
                                                   i == 0 ? g->e0 : nullptr, i + 1 == nsl ? g->e1 : nullptr, iv_cols));
             return IPCR_OK;
         };

@@ -616,12 +616,24 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
         }
         return b.str();
     };
+    // IPCR_JIT_INVMASK=1 (default): the inv plane of a column that holds no invalid base is all zero (the genome's column
+    // mask says which: kernels.hip, ipcr_colmask_set), so it is not fetched.  Every inv load of the wave's own block is a
+    // raw buffer load through a descriptor over that block; a clean lane's offset is 0x80000000, out of the descriptor's
+    // range, and the hardware returns zeros for it.  No branch: loads inside branches cost the prefetch depth (see
+    // IPCR_JIT_ROLL).  A third of the bytes of a sweep over a genome of ACGT only.  0: the inv plane is read everywhere.
+    const bool invmask = env_int("IPCR_JIT_INVMASK", 1, 0, 1) != 0;
+    const bool nt = env_int("IPCR_JIT_NT", 1, 0, 1) != 0; // every tile byte is read once: non-temporal loads
+    auto inv_load = [&](const std::string &q, bool stream) { // the inv words of quad q of the own block
+        if (invmask) return "__builtin_amdgcn_raw_buffer_load_b128(ivr, ivoff + (" + q + ") * 3072u, 0, " + (stream && nt ? "2" : "0") + ")";
+        if (stream && nt) return "__builtin_nontemporal_load(own + (" + q + ") * 192u + 128u)";
+        return "own[(" + q + ") * 192u + 128u]";
+    };
     auto load_normal = [&](const std::string &q) {
         const std::string d = std::to_string(D);
-        if (env_int("IPCR_JIT_NT", 1, 0, 1)) // every tile byte is read once: non-temporal loads
+        if (nt)
             return "p" + d + "lo = __builtin_nontemporal_load(own + (" + q + ") * 192u); p" + d + "hi = __builtin_nontemporal_load(own + (" + q +
-                   ") * 192u + 64u); p" + d + "iv = __builtin_nontemporal_load(own + (" + q + ") * 192u + 128u);";
-        return "p" + d + "lo = own[(" + q + ") * 192u]; p" + d + "hi = own[(" + q + ") * 192u + 64u]; p" + d + "iv = own[(" + q + ") * 192u + 128u];";
+                   ") * 192u + 64u); p" + d + "iv = " + inv_load(q, true) + ";";
+        return "p" + d + "lo = own[(" + q + ") * 192u]; p" + d + "hi = own[(" + q + ") * 192u + 64u]; p" + d + "iv = " + inv_load(q, true) + ";";
     };
     // rows past the strand end belong to the next strand: the same words shifted down one bit,
     // bit 31 coming from the neighbour column (lane + 1, or lane 0 of the next block).  The head
@@ -832,7 +844,8 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
     s << "};\n";
     s << "#define CAND_CAP " << CAND_CAP << "u\n";
     s << "// IPCR_WAVES_PER_GROUP " << WPG << "\n";
-    s << "extern \"C\" __global__ void __launch_bounds__(" << WPG * 64 << ", " << WPS << ") ipcr_filter(const v4* __restrict__ planes, u64 block0, u64 nblocks,\n"
+    s << "extern \"C\" __global__ void __launch_bounds__(" << WPG * 64 << ", " << WPS << ") ipcr_filter(const v4* __restrict__ planes, const u64* __restrict__ colmask,\n"
+         "    u64 block0, u64 nblocks,\n"
          "    qent* __restrict__ queue_all, u64 qcap, u64* __restrict__ qcount_all,\n"
          "    const u32* __restrict__ rst, const dpat* __restrict__ pats, const u64* __restrict__ rec_start,\n"
          "    const u64* __restrict__ rec_len, const u32* __restrict__ block_rec, u32 nrec, u32 max_mm, u32 check_rst,\n"
@@ -872,6 +885,12 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
     s << "  u64* qcount = qcount_all + shard * 16u;\n";
     s << "  const v4* own = planes + block * 6144ull + lane;\n";
     s << "  const v4* nblk = planes + (block + 1ull) * 6144ull; // column 0 of the next block\n";
+    if (invmask) { // block is wave-uniform; readfirstlane makes it provably so (a scalar mask load, a descriptor in SGPRs)
+        s << "  const u64 ublk = ((u64)(u32)__builtin_amdgcn_readfirstlane((u32)(block >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((u32)block);\n"
+             "  const u64 dirty = colmask[ublk]; // bit lane: this lane's column holds an invalid base\n"
+             "  const __amdgpu_buffer_rsrc_t ivr = __builtin_amdgcn_make_buffer_rsrc((void*)(planes + ublk * 6144ull), (short)0, 6144 * 16, 0x00020000);\n"
+             "  const u32 ivoff = ((dirty >> lane) & 1ull) ? lane * 16u + 2048u : 0x80000000u; // quad 0's inv word, or out of range: zeros\n";
+    }
     s << "  const u64 posbase = ((block * 64ull + lane) * 32ull) << 7;\n";
     s << "  u32 ";
     for (int i = 0; i < W; ++i) {
@@ -884,7 +903,9 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
     s << "  v4 (*st)[" << SC << "] = stash[wv];\n";
     for (int i = 1; i <= D; ++i) {
         const std::string at = seg ? "(seg_f0 * " + std::to_string(QPI) + "u + " + std::to_string(i - 1) + "u) * 192u" : std::to_string((i - 1) * 192);
-        s << "  v4 p" << i << "lo = own[" << at << "], p" << i << "hi = own[" << at << " + 64u], p" << i << "iv = own[" << at << " + 128u];\n";
+        const std::string atq = seg ? "seg_f0 * " + std::to_string(QPI) + "u + " + std::to_string(i - 1) + "u" : std::to_string(i - 1) + "u";
+        s << "  v4 p" << i << "lo = own[" << at << "], p" << i << "hi = own[" << at << " + 64u], p" << i << "iv = "
+          << (invmask ? inv_load(atq, false) : "own[" + at + " + 128u]") << ";\n";
     }
     if (nb_lds)
         s << "  v4 nbv = {0u, 0u, 0u, 0u}; // word (lane / 3, lane % 3) of the next block's column 0\n"
@@ -893,7 +914,7 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
         s << "  if (seg_e1 * " << QPI << "u + " << D << "u > 32u) {\n";
         for (int q = 0; q < QW; ++q)
             s << "    st[" << q * 3 << "][lane] = own[" << q * 192 << "]; st[" << q * 3 + 1 << "][lane] = own[" << q * 192 + 64 << "]; st["
-              << q * 3 + 2 << "][lane] = own[" << q * 192 + 128 << "];\n";
+              << q * 3 + 2 << "][lane] = " << (invmask ? inv_load(std::to_string(q) + "u", false) : "own[" + std::to_string(q * 192 + 128) + "]") << ";\n";
         if (nb_lds) s << "    if (lane < " << QW * 3 << "u) st[lane][64] = nbv;\n";
         s << "  }\n";
     }
@@ -2229,11 +2250,11 @@ JitFilter *small_form(JitFilter *f, int segs) {
 }
 } // namespace
 
-hipError_t jit_launch(JitFilter *f, hipStream_t st, const uint32_t *planes, uint64_t block0, uint64_t nblocks, void *queue,
-                      uint64_t qcap, unsigned long long *qcount, const JitVerify &v, hipEvent_t start, hipEvent_t stop) {
+hipError_t jit_launch(JitFilter *f, hipStream_t st, const uint32_t *planes, const uint64_t *colmask, uint64_t block0, uint64_t nblocks,
+                      void *queue, uint64_t qcap, unsigned long long *qcount, const JitVerify &v, hipEvent_t start, hipEvent_t stop) {
     if (nblocks == 0) return hipSuccess;
     JitVerify a = v;
-    void *args[] = {(void *)&planes, (void *)&block0, (void *)&nblocks, (void *)&queue, (void *)&qcap, (void *)&qcount,
+    void *args[] = {(void *)&planes, (void *)&colmask, (void *)&block0, (void *)&nblocks, (void *)&queue, (void *)&qcap, (void *)&qcount,
                     (void *)&a.rst, (void *)&a.pats, (void *)&a.rec_start, (void *)&a.rec_len, (void *)&a.block_rec, (void *)&a.nrec,
                     (void *)&a.max_mm, (void *)&a.check_rst, (void *)&a.hits, (void *)&a.hcap, (void *)&a.counts,
                     (void *)&a.next_counts, (void *)&a.next_qcount, (void *)&a.tickets, (void *)&a.pub,

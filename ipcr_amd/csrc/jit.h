@@ -57,9 +57,10 @@ struct JitVerify {
     uint32_t seq = 0;
     uint32_t withhold = 0; // tests: slot + 1 of a record published with a stale tag in its first half (a torn record)
 };
-// blocks [block0, block0 + nblocks) of the tiles
-hipError_t jit_launch(JitFilter *f, hipStream_t st, const uint32_t *planes, uint64_t block0, uint64_t nblocks, void *queue,
-                      uint64_t qcap, unsigned long long *qcount, const JitVerify &v, hipEvent_t start, hipEvent_t stop);
+// blocks [block0, block0 + nblocks) of the tiles; colmask: the genome's column mask (one word per block: which columns hold
+// an invalid base -- the filter fetches the inv plane of those only)
+hipError_t jit_launch(JitFilter *f, hipStream_t st, const uint32_t *planes, const uint64_t *colmask, uint64_t block0, uint64_t nblocks,
+                      void *queue, uint64_t qcap, unsigned long long *qcount, const JitVerify &v, hipEvent_t start, hipEvent_t stop);
 // launches that took the form for small launches (a block shared by several waves) so far, in this process: tests
 uint64_t jit_small_launches();
 // seed-index filter for large panels, with the panel's key shapes baked in (host.cpp: build_index)

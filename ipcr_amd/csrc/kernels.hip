@@ -31,6 +31,16 @@
 // 0.9 Tbases/s; no ballots, no atomics here either.
 // Semantics: inv = byte is not an upper-case A/C/G/T (core/primer/iupac.go:62-67); rst = byte is outside
 // ACGTacgt (core/engine/ac.go:16-30); bases past the record end are inv=1,rst=0 padding (staged as 'a').
+// Column mask (tile_layout.h): bit (col & 63) of word col >> 6 = some inv bit of column col is 1.  Every writer of a
+// column's tiles sets its bit exactly -- clean as well as dirty: a reused genome turns columns both ways, and a stale
+// clean bit would make the specialised filter read an N as A.  Columns of one block are written by several waves:
+// device-scope vector atomics (global_atomic_or / and_x2).
+__device__ __forceinline__ void ipcr_colmask_set(uint64_t *colmask, uint64_t col, bool dirty) {
+    const uint64_t bit = 1ull << (uint32_t)(col & 63u);
+    if (dirty) __hip_atomic_fetch_or(colmask + (col >> 6), bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else __hip_atomic_fetch_and(colmask + (col >> 6), ~bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __device__ __forceinline__ uint32_t swar_zero_bytes(uint32_t x) { // 0x80 in every byte of x that is zero, exactly
     const uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
     return ~(t | x) & 0x80808080u;
@@ -40,7 +50,7 @@ template <bool ALIGNED>
 __device__ __forceinline__ void pack_pair(const uint8_t *__restrict__ seq, uint64_t len, uint64_t col0, uint64_t ncol,
                                           uint64_t pairidx, uint32_t lane, uint32_t *mine,
                                           uint32_t *__restrict__ planes, uint32_t *__restrict__ rst,
-                                          uint32_t *__restrict__ rec_flags) {
+                                          uint64_t *__restrict__ colmask, uint32_t *__restrict__ rec_flags) {
     const uint64_t base = pairidx * 2u * IPCR_COLUMN_BASES; // record-local first base of my column pair
 #pragma unroll
     for (uint32_t it = 0; it < 8u; ++it) {
@@ -94,6 +104,8 @@ __device__ __forceinline__ void pack_pair(const uint8_t *__restrict__ seq, uint6
         *reinterpret_cast<uint4 *>(planes + ipcr_plane_word(block, q * 4u, 2, ln)) = make_uint4(oiv[0], oiv[1], oiv[2], oiv[3]);
         *reinterpret_cast<uint4 *>(rst + ipcr_rst_word(block, q * 4u, ln)) = make_uint4(ors[0], ors[1], ors[2], ors[3]);
     }
+    const uint64_t dirty = __ballot((oiv[0] | oiv[1] | oiv[2] | oiv[3]) != 0u); // half wave h = column h of the pair
+    if (q == 0u && pairidx * 2u + h < ncol) ipcr_colmask_set(colmask, col, ((dirty >> (32u * h)) & 0xFFFFFFFFull) != 0ull);
     const bool saw_rst = (ors[0] | ors[1] | ors[2] | ors[3]) != 0u;
     // bit 0 is the only bit a record's flag word ever gets: a plain store (idempotent, also right when the word lives
     // in pinned host memory, where the chunk path keeps it -- no copy operation brings it back)
@@ -104,6 +116,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ s
                                                    uint64_t col0, uint64_t ncol,
                                                    uint32_t *__restrict__ planes,
                                                    uint32_t *__restrict__ rst,
+                                                   uint64_t *__restrict__ colmask,
                                                    uint32_t *__restrict__ rec_flags,
                                                    uint64_t *__restrict__ rec_start_out,
                                                    uint64_t *__restrict__ rec_len_out) {
@@ -115,7 +128,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ s
     }
     const uint64_t pairidx = (uint64_t)blockIdx.x * 4u + wv;
     if (pairidx * 2u >= ncol) return; // waves are independent (no workgroup barrier)
-    pack_pair<true>(seq, len, col0, ncol, pairidx, lane, s_in[wv], planes, rst, rec_flags);
+    pack_pair<true>(seq, len, col0, ncol, pairidx, lane, s_in[wv], planes, rst, colmask, rec_flags);
 }
 
 // many records in one launch (a nested-PCR batch or a fragmented assembly has thousands of short records, one launch
@@ -124,7 +137,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ s
 __global__ __launch_bounds__(256) void pack_batch_kernel(const uint8_t *__restrict__ base, const ipcr_pack_rec *__restrict__ recs,
                                                          const uint32_t *__restrict__ pair_prefix, uint32_t nrec,
                                                          uint32_t *__restrict__ planes, uint32_t *__restrict__ rst,
-                                                         uint32_t *__restrict__ rec_flags) {
+                                                         uint64_t *__restrict__ colmask, uint32_t *__restrict__ rec_flags) {
     __shared__ uint32_t s_in[4][2048];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     const uint64_t gp = (uint64_t)blockIdx.x * 4u + wv;
@@ -135,7 +148,7 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const uint8_t *__restri
         if (pair_prefix[mid] <= gp) lo = mid; else hi = mid;
     }
     const ipcr_pack_rec r = recs[lo];
-    pack_pair<false>(base + r.src_off, r.len, r.col0, r.ncol, gp - pair_prefix[lo], lane, s_in[wv], planes, rst, rec_flags + r.flag_idx);
+    pack_pair<false>(base + r.src_off, r.len, r.col0, r.ncol, gp - pair_prefix[lo], lane, s_in[wv], planes, rst, colmask, rec_flags + r.flag_idx);
 }
 
 // fill columns [col_begin, col_end) with padding (inv=1, everything else 0)
@@ -166,7 +179,7 @@ __global__ __launch_bounds__(256) void tiles_from_linear_kernel(const uint4 *__r
                                                                const uint4 *__restrict__ lin_iv, const uint4 *__restrict__ lin_rs,
                                                                const uint32_t *__restrict__ iv_cols, // null, or one bit per column of the launch: its invalid bits are in lin_iv (else: made here)
                                                                uint64_t rec_col0, uint64_t col0, uint64_t ncol, uint64_t len,
-                                                               uint32_t *__restrict__ planes, uint32_t *__restrict__ rst,
+                                                               uint32_t *__restrict__ planes, uint32_t *__restrict__ rst, uint64_t *__restrict__ colmask,
                                                                uint64_t *__restrict__ rec_start_out, uint64_t *__restrict__ rec_len_out) {
     if (rec_start_out && blockIdx.x == 0 && threadIdx.x == 0) { // chunk path: the one record's table entries, no copy operation
         rec_start_out[0] = rec_col0 * IPCR_COLUMN_BASES;
@@ -192,9 +205,11 @@ __global__ __launch_bounds__(256) void tiles_from_linear_kernel(const uint4 *__r
         v = make_uint4(w[0], w[1], w[2], w[3]);
     }
     const uint32_t t0 = tl_transpose(v.x, lane), t1 = tl_transpose(v.y, lane), t2 = tl_transpose(v.z, lane), t3 = tl_transpose(v.w, lane);
+    const uint64_t dirty = __ballot((v.x | v.y | v.z | v.w) != 0u) >> (threadIdx.x & 32u); // this half wave's lanes in bits 0..31
     if (!live) return;
     const uint64_t col = col0 + c, block = col >> 6;
     const uint32_t ln = (uint32_t)(col & 63u);
+    if (plane == 2u && lane == 0u) ipcr_colmask_set(colmask, col, (dirty & 0xFFFFFFFFull) != 0ull); // the transpose keeps the set of bits
     if (plane < 3u) {
         planes[ipcr_plane_word(block, lane, plane, ln)] = t0;
         planes[ipcr_plane_word(block, 32u + lane, plane, ln)] = t1;
@@ -208,7 +223,7 @@ __global__ __launch_bounds__(256) void tiles_from_linear_kernel(const uint4 *__r
     }
 }
 
-__global__ void fill_pad_kernel(uint32_t *__restrict__ planes, uint32_t *__restrict__ rst,
+__global__ void fill_pad_kernel(uint32_t *__restrict__ planes, uint32_t *__restrict__ rst, uint64_t *__restrict__ colmask,
                                 uint64_t col_begin, uint64_t col_end) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; // (column, row)
     const uint64_t col = col_begin + (i >> 7);
@@ -220,6 +235,7 @@ __global__ void fill_pad_kernel(uint32_t *__restrict__ planes, uint32_t *__restr
     planes[ipcr_plane_word(block, row, 1, ln)] = 0u;
     planes[ipcr_plane_word(block, row, 2, ln)] = 0xFFFFFFFFu;
     rst[ipcr_rst_word(block, row, ln)] = 0u;
+    if (row == 0u) ipcr_colmask_set(colmask, col, true); // padding is invalid
 }
 
 // -------------------------------------------------------------------------- reset bytes per window
@@ -760,14 +776,14 @@ __global__ __launch_bounds__(THREADS) void probe_tiles_kernel(const uint32_t *__
 namespace ipcr {
 
 hipError_t launch_pack(hipStream_t st, const uint8_t *seq, uint64_t len, uint64_t col0, uint64_t ncol,
-                       uint32_t *planes, uint32_t *rst, uint32_t *rec_flags, uint64_t *rec_start_out, uint64_t *rec_len_out,
+                       uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint32_t *rec_flags, uint64_t *rec_start_out, uint64_t *rec_len_out,
                        hipEvent_t start, hipEvent_t stop) {
     const uint64_t pairs = (ncol + 1u) / 2u;
     const uint64_t grid = (pairs + 3u) / 4u;
     if (grid == 0) return hipSuccess;
     // start / stop ride on the dispatch itself (its begin and end timestamps): no marker packets around the kernel
     hipExtLaunchKernelGGL(pack_kernel, dim3((uint32_t)grid), dim3(256), 0, st, start, stop, 0,
-                          seq, len, col0, ncol, planes, rst, rec_flags, rec_start_out, rec_len_out);
+                          seq, len, col0, ncol, planes, rst, colmask, rec_flags, rec_start_out, rec_len_out);
     return hipGetLastError();
 }
 
@@ -775,22 +791,22 @@ hipError_t launch_pack(hipStream_t st, const uint8_t *seq, uint64_t len, uint64_
 // its length: the table entries the kernel writes for the chunk path are the record's, whatever slice a launch converts)
 hipError_t launch_tiles_from_linear(hipStream_t st, const uint32_t *lin_lo, const uint32_t *lin_hi, const uint32_t *lin_iv,
                                     const uint32_t *lin_rs, uint64_t rec_col0, uint64_t col0, uint64_t ncol, uint64_t len,
-                                    uint32_t *planes, uint32_t *rst, uint64_t *rec_start_out, uint64_t *rec_len_out,
+                                    uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint64_t *rec_start_out, uint64_t *rec_len_out,
                                     hipEvent_t start, hipEvent_t stop, const uint32_t *iv_cols) {
     const uint64_t grid = (ncol * 4u + 7u) / 8u; // 8 half waves per workgroup
     if (grid == 0) return hipSuccess;
     hipExtLaunchKernelGGL(tiles_from_linear_kernel, dim3((uint32_t)grid), dim3(256), 0, st, start, stop, 0,
                           reinterpret_cast<const uint4 *>(lin_lo), reinterpret_cast<const uint4 *>(lin_hi),
                           reinterpret_cast<const uint4 *>(lin_iv), reinterpret_cast<const uint4 *>(lin_rs), iv_cols, rec_col0, col0, ncol, len,
-                          planes, rst, rec_start_out, rec_len_out);
+                          planes, rst, colmask, rec_start_out, rec_len_out);
     return hipGetLastError();
 }
 
 hipError_t launch_pack_batch(hipStream_t st, const uint8_t *base, const ipcr_pack_rec *recs, const uint32_t *pair_prefix,
-                             uint32_t nrec, uint64_t total_pairs, uint32_t *planes, uint32_t *rst, uint32_t *rec_flags) {
+                             uint32_t nrec, uint64_t total_pairs, uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint32_t *rec_flags) {
     const uint64_t grid = (total_pairs + 3u) / 4u;
     if (grid == 0 || nrec == 0) return hipSuccess;
-    pack_batch_kernel<<<dim3((uint32_t)grid), dim3(256), 0, st>>>(base, recs, pair_prefix, nrec, planes, rst, rec_flags);
+    pack_batch_kernel<<<dim3((uint32_t)grid), dim3(256), 0, st>>>(base, recs, pair_prefix, nrec, planes, rst, colmask, rec_flags);
     return hipGetLastError();
 }
 
@@ -800,10 +816,10 @@ hipError_t launch_window_reset(hipStream_t st, const uint32_t *rst, const uint64
     return hipGetLastError();
 }
 
-hipError_t launch_fill_pad(hipStream_t st, uint32_t *planes, uint32_t *rst, uint64_t col_begin, uint64_t col_end) {
+hipError_t launch_fill_pad(hipStream_t st, uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint64_t col_begin, uint64_t col_end) {
     if (col_end <= col_begin) return hipSuccess;
     const uint64_t n = (col_end - col_begin) * 128u;
-    fill_pad_kernel<<<dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, st>>>(planes, rst, col_begin, col_end);
+    fill_pad_kernel<<<dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, st>>>(planes, rst, colmask, col_begin, col_end);
     return hipGetLastError();
 }
 
