@@ -259,7 +259,8 @@ ipcr_status ipcr_genome_add_record_device(ipcr_genome *g, const void *dev_seq, u
  * jump-ahead (core/engine/performance_benchmark_test.go:67-76); bit-identical to bases
  * [stream_offset, stream_offset + len) of the serial loop started from `seed` */
 ipcr_status ipcr_lcg_fill_device(void *dev_out, uint64_t len, uint32_t seed, uint64_t stream_offset);
-/* copy bases of a resident record back to the host (decoded from the tiles; invalid -> 'N') */
+/* copy bases of a resident record back to the host (decoded from the tiles; invalid -> 'N', so a byte outside
+ * ACGTacgt comes back as 'N': ipcr_genome_read_windows below returns the exact bytes) */
 ipcr_status ipcr_genome_read(const ipcr_genome *g, uint32_t record, uint64_t pos, uint8_t *out, uint64_t len);
 uint32_t ipcr_genome_num_records(const ipcr_genome *g);
 uint64_t ipcr_genome_record_len(const ipcr_genome *g, uint32_t record);
@@ -438,6 +439,16 @@ typedef struct ipcr_nested_hit {
 } ipcr_nested_hit;
 ipcr_status ipcr_nested_windows(const ipcr_genome *g, const ipcr_window *windows, int64_t n, const ipcr_panel *inner,
                                 ipcr_scratch *inner_scratch, ipcr_nested_hit *out);
+/* exact bytes of n windows of a resident genome, concatenated: window i is out[offsets[i] .. offsets[i+1]) (offsets: n + 1
+ * entries).  ipcr_window as for ipcr_nested_windows: [start, end) of `record`, or record[start:] ++ record[:end] when
+ * start > end.  The bytes are the record as loaded: the normalised FASTA text (core/fasta/normalize.go:5-14), or the bytes
+ * given to ipcr_genome_add_record*.  *needed = total bytes; IPCR_ERR_CAPACITY (offsets and *needed written, out untouched)
+ * when cap < *needed; IPCR_ERR_INVALID for a window outside its record; IPCR_ERR_UNSUPPORTED when the genome dropped its
+ * exception runs (more than its bound).  Safe from several threads at once, next to scans on other scratches. */
+ipcr_status ipcr_genome_read_windows(const ipcr_genome *g, const ipcr_window *windows, int64_t n, uint8_t *out,
+                                     uint64_t cap, uint64_t *offsets, uint64_t *needed);
+/* runs of bytes outside ACGTacgtN the genome keeps (UINT64_MAX: dropped, see above) */
+uint64_t ipcr_genome_exception_runs(const ipcr_genome *g);
 /* every product of the last scan on `outer` (out[i] <-> product i) */
 ipcr_status ipcr_nested_products(const ipcr_scratch *outer, const ipcr_genome *g, const ipcr_panel *inner,
                                  ipcr_scratch *inner_scratch, ipcr_nested_hit *out, int64_t n_out);

@@ -124,7 +124,27 @@ func scanFile(fa string, pc pipeline.Config, pairs []primer.Pair, ec engine.Conf
 		return lastErr()
 	}
 	windows := unsafe.Slice(wins, int(nw))
-	for _, cpr := range unsafe.Slice(prods, int(n)) {
+	cprods := unsafe.Slice(prods, int(n))
+	// the bases of every product's window, exact (bytes outside ACGTacgt included), in ONE call for all of them
+	// (pipeline.go:80-89, engine.go:175-183)
+	var amps []byte
+	var offs []C.uint64_t
+	if (pc.NeedSeq || ec.NeedSites) && len(cprods) > 0 {
+		rw := make([]C.ipcr_window, len(cprods))
+		total := uint64(0)
+		for i, cpr := range cprods {
+			cw := windows[int(cpr.record)]
+			rw[i] = C.ipcr_window{start: C.int64_t(int64(cw.start) + int64(cpr.start)), end: C.int64_t(int64(cw.start) + int64(cpr.end)), record: C.int32_t(cw.record)}
+			total += uint64(cpr.end - cpr.start)
+		}
+		amps = make([]byte, total+1)
+		offs = make([]C.uint64_t, len(cprods)+1)
+		var needed C.uint64_t
+		if C.ipcr_genome_read_windows(g, &rw[0], C.int64_t(len(rw)), (*C.uint8_t)(unsafe.Pointer(&amps[0])), C.uint64_t(total), &offs[0], &needed) != C.IPCR_OK {
+			return lastErr()
+		}
+	}
+	for i, cpr := range cprods {
 		cw := windows[int(cpr.record)]
 		pair := pairs[int(cpr.pair)]
 		// what the worker would have sent: the window's ID and window-local coordinates ...
@@ -141,11 +161,8 @@ func scanFile(fa string, pc pipeline.Config, pairs []primer.Pair, ec engine.Conf
 		}
 		pr.FwdMismatchIdx = idx(cpr.fwd_idx[:], int(cpr.n_fwd_idx))
 		pr.RevMismatchIdx = idx(cpr.rev_idx[:], int(cpr.n_rev_idx))
-		if pc.NeedSeq || ec.NeedSites { // the window's bases, read back from the resident tiles (pipeline.go:80-89, engine.go:175-183)
-			amp := make([]byte, pr.End-pr.Start)
-			if len(amp) > 0 && C.ipcr_genome_read(g, cw.record, C.uint64_t(uint64(cw.start)+uint64(pr.Start)), (*C.uint8_t)(unsafe.Pointer(&amp[0])), C.uint64_t(len(amp))) != C.IPCR_OK {
-				return lastErr()
-			}
+		if pc.NeedSeq || ec.NeedSites { // the window's bases, from the one read above
+			amp := amps[offs[i]:offs[i+1]]
 			if pc.NeedSeq {
 				pr.Seq = string(amp)
 			}

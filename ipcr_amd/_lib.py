@@ -124,6 +124,9 @@ SYMBOLS = {
     "ipcr_genome_add_record_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "ipcr_lcg_fill_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64]),
     "ipcr_genome_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_char_p, C.c_uint64]),
+    "ipcr_genome_read_windows": (C.c_int, [C.c_void_p, C.POINTER(Window), C.c_int64, C.c_void_p, C.c_uint64,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ipcr_genome_exception_runs": (C.c_uint64, [C.c_void_p]),
     "ipcr_genome_num_records": (C.c_uint32, [C.c_void_p]),
     "ipcr_genome_record_len": (C.c_uint64, [C.c_void_p, C.c_uint32]),
     "ipcr_genome_record_id": (C.c_char_p, [C.c_void_p, C.c_uint32]),

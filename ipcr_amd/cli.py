@@ -3,7 +3,8 @@
 Only what sits directly either side of the scan path ("next" 1 and 2):
 FASTA -> resident tiles, the collector's total product order, and the text/TSV rows -- with the
 reference's flag names and defaults (internal/clibase/common.go:61-110) so outputs can be
-diffed against `ipcr`.  Thermo scoring, pretty blocks, JSON and nested PCR are out of scope.
+diffed against `ipcr`.  --products (JSONL `seq`) and --output fasta carry the amplicon bytes, read exactly from the
+resident genome (ipcr_genome_read_windows).  Thermo scoring, pretty blocks, JSON and nested PCR are out of scope.
 
     python -m ipcr_amd.cli -f AGAGTTTGATCMTGGCTCAG -r TACGGYTACCTTGTTAYGACTT --mismatches 0 demo.fa
 """
@@ -141,9 +142,10 @@ def format_row(source_file: str, p: engine.Product) -> str:
                       str(p.FwdMM), str(p.RevMM), ints_csv(p.FwdMismatchIdx), ints_csv(p.RevMismatchIdx)])
 
 
-def format_jsonl(source_file: str, p: engine.Product) -> str:
+def format_jsonl(source_file: str, p: engine.Product, seq: str = "") -> str:
     """One line of --output jsonl: api.ProductV1 (pkg/api/products_v1.go:6-25) as encoding/json writes it -- field
-    order of the struct, zero / empty `omitempty` fields left out, compact separators, <, > and & escaped."""
+    order of the struct, zero / empty `omitempty` fields left out, compact separators, <, > and & escaped.  `seq`
+    (--products) goes between rev_mm_i and source_file, left out when empty."""
     import json
     d = {"experiment_id": p.ExperimentID, "sequence_id": p.SequenceID, "start": p.Start, "end": p.End,
          "length": p.Length, "type": p.Type}
@@ -155,10 +157,44 @@ def format_jsonl(source_file: str, p: engine.Product) -> str:
         d["fwd_mm_i"] = list(p.FwdMismatchIdx)
     if p.RevMismatchIdx:
         d["rev_mm_i"] = list(p.RevMismatchIdx)
+    if seq:
+        d["seq"] = seq
     if source_file:
         d["source_file"] = source_file
     text = json.dumps(d, separators=(",", ":"), ensure_ascii=False)
     return text.replace("<", "\\u003c").replace(">", "\\u003e").replace("&", "\\u0026")
+
+
+def format_fasta(idx: int, source_file: str, p: engine.Product, seq: str) -> str:
+    """One record of --output fasta -- internal/output/fasta.go:11-44 (without the final newline)."""
+    return f">{p.ExperimentID}_{idx} start={p.Start} end={p.End} len={p.Length} source_file={source_file}\n{seq}"
+
+
+def fasta_records(rows, sort: bool) -> List[str]:
+    """--output fasta over (source_file, product, seq) rows: products with an empty sequence are skipped.  Unsorted
+    (StreamFASTA) the index counts the records written; --sort (WriteFASTA) it is the position in the sorted list + 1
+    (internal/writers/product.go:66-80)."""
+    out, written = [], 0
+    for i, (path, p, seq) in enumerate(rows):
+        if not seq:
+            continue
+        written += 1
+        out.append(format_fasta(i + 1 if sort else written, path, p, seq))
+    return out
+
+
+def _text(b: bytes) -> str:
+    return b.decode("latin-1")  # one character per byte: bytes >= 0x80 are kept as they were loaded
+
+
+def _record_seqs(path: str, wanted) -> dict:
+    """whole records of a file, streamed on the host (the fallback when the genome keeps no exception runs)"""
+    from . import fasta
+    out = {}
+    for i, rec in enumerate(fasta.StreamChunks(path, 0, 0)):
+        if i in wanted:
+            out[i] = bytes(rec.Seq)
+    return out
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -176,7 +212,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--seed-length", type=int, default=12)
     ap.add_argument("--circular", "-c", action="store_true")
     ap.add_argument("--sort", action="store_true")
-    ap.add_argument("--output", "-o", default="text", choices=["text", "jsonl"])
+    ap.add_argument("--output", "-o", default="text", choices=["text", "jsonl", "fasta"])
+    ap.add_argument("--products", action="store_true", help="carry each product's sequence (JSONL field `seq`)")
     ap.add_argument("--no-header", action="store_true")
     ap.add_argument("--multiplex", action="store_true", help="ipcr-multiplex self-pair rule (unique oligos)")
     ap.add_argument("--probe", "-P", default="")
@@ -214,6 +251,10 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
     if not seq_files:
         print("error: no FASTA input", file=stderr)
         return 2
+    need_seq = o.products or o.output == "fasta"
+    if o.probe and need_seq:
+        print("error: --probe does not support --products or --output fasta", file=stderr)
+        return 2
     tw = o.terminal_window if o.terminal_window >= 1 else 0            # runutil.EffectiveTerminalWindow
     cfg = engine.Config(MaxMM=o.mismatches, TerminalWindow=tw, MinLen=o.min_length, MaxLen=o.max_length,
                         HitCap=o.hit_cap, SeedLen=o.seed_length, Circular=o.circular)
@@ -246,7 +287,11 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
                     probe_hits = [out[i] for i in range(len(prods))]
                 w, nw = C.POINTER(_lib.ChunkWindow)(), C.c_int64()
                 _lib.check(_lib.lib().ipcr_scratch_chunk_windows(sc._h, C.byref(w), C.byref(nw)))
-                for p, h in zip(prods, probe_hits):
+                seqs = [""] * len(prods)
+                if need_seq and prods:  # window-local coordinates -> the record's (ERR_UNSUPPORTED: stream the chunks)
+                    seqs = [_text(b) for b in g.read_windows([(w[p.Record].record, w[p.Record].start + p.Start,
+                                                                w[p.Record].start + p.End) for p in prods])]
+                for p, h, sq in zip(prods, probe_hits, seqs):
                     ph = None
                     if h is not None:
                         if o.require_probe and not h.found:                 # internal/visitors/probe.go:20-22
@@ -259,7 +304,7 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
                         ph = (h, site)
                     p = collector.add(path, p)
                     if p is not None:
-                        rows.append((path, p, ph))
+                        rows.append((path, p, ph, sq))
                 g.close()
                 continue
             except _lib.IpcrError as e:
@@ -279,6 +324,7 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
                     # collector rebases them (pipeline.go:80-89 slices Product.Seq chunk-locally too)
                     hits = sc.probe_products(o.probe, o.probe_max_mm) if o.probe and prods else [None] * len(prods)
                     for p, h in zip(prods, hits):
+                        sq = _text(bytes(rec.Seq[p.Start:p.End])) if need_seq else ""
                         ph = None
                         if h is not None:
                             if o.require_probe and not h.found:             # internal/visitors/probe.go:20-22
@@ -289,7 +335,7 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
                             ph = (h, site)
                         p = collector.add(path, p)
                         if p is not None:
-                            rows.append((path, p, ph))
+                            rows.append((path, p, ph, sq))
             except _lib.IpcrError as e:
                 print(f"error: {e}", file=stderr)
             continue
@@ -302,6 +348,16 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
             print(f"error: {e}", file=stderr)       # pipeline.go:174-182: record the error, go on
             continue
         prods = eng.ScanGenome(g, cp, sc)
+        seqs = [""] * len(prods)
+        if need_seq and prods:
+            win = [(p.Record, p.Start, p.End) for p in prods]  # start > end: a product across the origin
+            try:
+                seqs = [_text(b) for b in g.read_windows(win)]
+            except _lib.IpcrError as e:
+                if e.status != _lib.ERR_UNSUPPORTED:
+                    raise
+                recs = _record_seqs(path, {r for r, _, _ in win})  # (the genome keeps no exception runs: stream the records)
+                seqs = [_text(recs[r][s:e] if s <= e else recs[r][s:] + recs[r][:e]) for r, s, e in win]
         probe_hits = None
         if o.probe:
             out = (_lib.ProbeHit * max(len(prods), 1))()
@@ -309,7 +365,7 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
             probe_hits = [out[i] for i in range(len(prods))]
         for i, p in enumerate(prods):
             if probe_hits is None:
-                rows.append((path, p, None))
+                rows.append((path, p, None, seqs[i]))
                 continue
             h = probe_hits[i]
             if o.require_probe and not h.found:                         # internal/visitors/probe.go:20-22
@@ -319,24 +375,28 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
                 amp = (g.read(p.Record, p.Start, p.End - p.Start) if p.Start <= p.End else
                        g.read(p.Record, p.Start, g.record_len(p.Record) - p.Start) + g.read(p.Record, 0, p.End))
                 site = amp.upper()[h.pos:h.pos + len(primer.Normalize(o.probe))].decode()
-            rows.append((path, p, (h, site)))
+            rows.append((path, p, (h, site), ""))
         g.close()
     if not chunk:  # the collector sees every product in the reference, chunked or not (ids.go quirk included)
         kept = []
-        for path, p, ph in rows:
+        for path, p, ph, sq in rows:
             p = collector.add(path, p)
             if p is not None:
-                kept.append((path, p, ph))
+                kept.append((path, p, ph, sq))
         rows = kept
     if o.sort:
         rows.sort(key=lambda t: product_sort_key(t[0], t[1]))
     if o.output == "jsonl" and not o.probe:
-        for path, p, _ in rows:
-            print(format_jsonl(path, p), file=stdout)
+        for path, p, _, sq in rows:
+            print(format_jsonl(path, p, sq if o.products else ""), file=stdout)
+        return o.no_match_exit_code if (not rows and o.no_match_exit_code) else 0
+    if o.output == "fasta":
+        for rec in fasta_records([(path, p, sq) for path, p, _, sq in rows], o.sort):
+            print(rec, file=stdout)
         return o.no_match_exit_code if (not rows and o.no_match_exit_code) else 0
     if not o.no_header:
         print(TSV_HEADER_PROBE if o.probe else TSV_HEADER, file=stdout)
-    for path, p, ph in rows:
+    for path, p, ph, _ in rows:
         line = format_row(path, p)
         if o.probe:                                                      # probeoutput/text.go:11-28
             h, site = ph

@@ -40,6 +40,14 @@ struct ipcr_amp_seg { // amplicon = [pa, pa+len_a) ++ [pb, pb+len_b) in padded c
     uint64_t pa, len_a, pb, len_b, out_off;
 };
 
+// exception run: `len` bytes of value `byte` from padded position `pos` -- a byte outside ACGTacgtN, which the tiles
+// decode as 'N' (DESIGN 9).  A genome's list is sorted by pos, runs never overlap, adjacent runs of one byte are merged.
+struct ipcr_exc_run {
+    uint64_t pos;
+    uint32_t len;
+    uint8_t byte, pad[3];
+};
+
 struct ipcr_probe_rec { // layout-identical to ipcr_probe_hit
     int32_t found, strand, pos, mm;
 };

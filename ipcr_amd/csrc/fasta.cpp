@@ -63,6 +63,9 @@ extern ipcr_status ipcr_internal_fail(ipcr_status st, const char *fmt, ...);
 // host.cpp: pack a record that already lies in device memory (16-byte aligned) and remember its ID
 extern ipcr_status ipcr_internal_genome_add_device(ipcr_genome *g, const uint8_t *dseq, uint64_t len, const char *id);
 extern hipStream_t ipcr_internal_genome_stream(ipcr_genome *g);
+// host.cpp: check the exception runs of the pack launches not yet checked (and repeat them if the store overflowed) --
+// before their source bytes are overwritten or freed.  Waits for the genome's stream only if such a launch exists.
+extern ipcr_status ipcr_internal_genome_settle(ipcr_genome *g);
 extern int ipcr_internal_genome_phys_device(const ipcr_genome *g);
 // host.cpp: records lying anywhere in one device buffer, packed by one launch (d_tmp: room for the record table)
 extern ipcr_status ipcr_internal_genome_add_batch(ipcr_genome *g, const uint8_t *dbase, const uint64_t *offs, const uint64_t *lens,
@@ -389,6 +392,10 @@ struct FastaLoader {
 
     ipcr_status append(uint64_t a, uint64_t b) { // compacted bytes [a, b) of this slab belong to the open record
         if (!have_id || b <= a) return IPCR_OK;
+        if (rec_len == 0) { // the record buffer is about to be refilled: the last record packed from it must be settled
+            const ipcr_status es = ipcr_internal_genome_settle(g);
+            if (es != IPCR_OK) return es;
+        }
         const uint64_t need = rec_len + (b - a);
         if (need > rec_cap) {
             uint64_t want = std::max<uint64_t>(need + (need >> 2), (uint64_t)1 << 20);
@@ -613,18 +620,24 @@ struct FastaLoader {
                 open_in_slab = true;
                 rec_len = 0;
             }
-            if (last && have_id && open_in_slab) { // the file ends here: the open record is complete too
+            const bool closes = last && have_id && open_in_slab;
+            if (closes) { // the file ends here: the open record is complete too
                 b_off.push_back(a); b_len.push_back(total - a); b_id.push_back(id);
                 count_record();
                 have_id = false;
-            } else {
+            }
+            // (waits for the stream: the record table is a host vector of that call; it also settles the exception runs of a
+            // record finished above, before the record buffer is refilled below)
+            s = flush_batch();
+            if (s != IPCR_OK) return s;
+            if (!closes) {
                 s = append(a, total);
                 if (s != IPCR_OK) return s;
             }
             open_in_slab = false; // whatever is still open continues in the record buffer
-            s = flush_batch();    // (waits for the stream: the record table is a host vector of that call)
-            if (s != IPCR_OK) return s;
             FHIP(hipStreamSynchronize(st)); // d_out is reused by the next slab
+            s = ipcr_internal_genome_settle(g); // (no wait: the one above covers every launch)
+            if (s != IPCR_OK) return s;
             t_pack += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count();
             mark("packed", j);
             if (cut > 0) {
@@ -638,7 +651,8 @@ struct FastaLoader {
             cv.notify_all();
             if (last) break; // cut == n: everything has been consumed
         }
-        const ipcr_status fs = finish_record();
+        ipcr_status fs = finish_record();
+        { const ipcr_status es = ipcr_internal_genome_settle(g); if (fs == IPCR_OK) fs = es; } // (the record buffer is freed with the loader)
         if (getenv("IPCR_DEBUG_TIMES"))
             fprintf(stderr, "fasta loader: buffers %.3f s, read %.3f s (overlapped), cut + header search %.3f s, h2d + decode %.3f s, copy + pack %.3f s\n",
                     t_alloc, t_read, t_host, t_decode, t_pack);
@@ -785,6 +799,7 @@ ipcr_status ipcr_genome_add_fasta(ipcr_genome *g, const char *path, uint32_t *n_
     FastaLoader L;
     ipcr_status st = L.open(g, path);
     if (st == IPCR_OK) st = L.run();
+    { const ipcr_status es = ipcr_internal_genome_settle(g); if (st == IPCR_OK) st = es; } // (an early return of run(): before L frees its buffers)
     if (n_added) *n_added = L.n_added;
     if (ids_needed) *ids_needed = L.ids.size() + 1;
     if (ids_out && cap) {

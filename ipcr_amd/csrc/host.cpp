@@ -1103,6 +1103,22 @@ struct ipcr_genome {
     bool shared_stream = false; // stream belongs to a scratch (its private chunk genome): never destroyed here
     hipEvent_t e0 = nullptr, e1 = nullptr;
     double pack_ms = 0;
+    // exception runs: the bytes outside ACGTacgtN, which the tiles decode as 'N'.  The device writers append them
+    // to d_exc behind its sorted prefix (exc_sorted runs) and count them in *d_exc_count (the word behind d_colmask), read
+    // back into *h_exc_count before their wait; the host-packed writers collect them in exc_host.  genome_finalize sorts,
+    // merges and uploads.  Launches not yet checked against the capacity wait in exc_redo, to be repeated if it overflowed.
+    bool exc_capture = true;      // false: a scratch-private genome (its caller holds the bytes)
+    bool exc_dropped = false;     // more runs than exc_bound: the store is gone, ipcr_genome_read_windows is unsupported
+    ipcr_exc_run *d_exc = nullptr;
+    uint64_t exc_cap = 0, exc_bound = 0;
+    unsigned long long *d_exc_count = nullptr;
+    uint64_t *h_exc_count = nullptr; // pinned
+    uint64_t exc_known = 0;          // device count when the pending launches began
+    uint64_t exc_sorted = 0;         // leading runs of d_exc that are sorted and merged: what the read uses
+    bool exc_dirty = false;          // runs arrived since the last finalize
+    std::vector<ipcr_exc_run> exc_host;
+    std::vector<std::function<hipError_t(uint64_t cap)>> exc_redo;
+    std::mutex read_mu; // ipcr_genome_read_windows / ipcr_genome_exception_runs may finalize from several threads
 };
 
 namespace {
@@ -1122,9 +1138,18 @@ ipcr_status genome_alloc(ipcr_genome *g, uint64_t cap_cols, uint32_t max_records
     HIPCHK(hipMalloc((void **)&g->d_rec_start, (uint64_t)max_records * 8ull));
     HIPCHK(hipMalloc((void **)&g->d_block_rec, (blocks + 1) * 4ull));
     HIPCHK(hipMalloc((void **)&g->d_rec_len, (uint64_t)max_records * 8ull));
-    HIPCHK(hipMalloc((void **)&g->d_colmask, (blocks + 1) * 8ull));
+    HIPCHK(hipMalloc((void **)&g->d_colmask, (blocks + 2) * 8ull)); // (+ the exception run counter)
+    g->d_exc_count = reinterpret_cast<unsigned long long *>(g->d_colmask + blocks + 1);
     HIPCHK(hipMemset(g->d_flags, 0, (uint64_t)max_records * 4ull));
     HIPCHK(hipMemset(g->d_colmask, 0xFF, (blocks + 1) * 8ull)); // every column dirty until a tile writer says otherwise
+    HIPCHK(hipMemset(g->d_exc_count, 0, 8));
+    HIPCHK(hipHostMalloc((void **)&g->h_exc_count, 8, hipHostMallocDefault));
+    *g->h_exc_count = 0;
+    {   // at most as many bytes as the rst plane (16 bytes per 128 bases); IPCR_TEST_EXCEPTION_MAX lowers it
+        g->exc_bound = std::max<uint64_t>(65536, g->cap_cols * IPCR_COLUMN_BASES / 128);
+        const char *e = getenv("IPCR_TEST_EXCEPTION_MAX");
+        if (e && *e) g->exc_bound = std::min<uint64_t>(g->exc_bound, strtoull(e, nullptr, 10));
+    }
     HIPCHK(hipStreamSynchronize(nullptr)); // (the fill runs on the null stream; the genome's stream is non-blocking and must not overtake it)
     return IPCR_OK;
 }
@@ -1139,6 +1164,12 @@ void genome_free_buffers(ipcr_genome *g) {
     if (g->d_rec_len) (void)hipFree(g->d_rec_len);
     if (g->d_colmask) (void)hipFree(g->d_colmask);
     g->d_colmask = nullptr;
+    g->d_exc_count = nullptr;
+    if (g->d_exc) (void)hipFree(g->d_exc);
+    g->d_exc = nullptr;
+    g->exc_cap = 0;
+    if (g->h_exc_count) (void)hipHostFree(g->h_exc_count);
+    g->h_exc_count = nullptr;
     g->planes = g->rst = g->d_flags = nullptr;
     g->d_rec_start = g->d_rec_len = nullptr;
 }
@@ -1154,6 +1185,13 @@ void genome_clear(ipcr_genome *g, bool flags_elsewhere = false) { // forget the 
     g->tables_dirty = true;
     g->next_col = 0;
     g->total_bases = 0;
+    if (g->exc_capture) {
+        if (g->d_exc_count) (void)hipMemsetAsync(g->d_exc_count, 0, 8, g->stream);
+        g->exc_known = g->exc_sorted = 0;
+        g->exc_dirty = g->exc_dropped = false;
+        g->exc_host.clear();
+        g->exc_redo.clear();
+    }
 }
 
 void genome_account_record(ipcr_genome *g, uint64_t len, uint64_t cols) { // a record's tiles are (being) written at next_col
@@ -1167,6 +1205,110 @@ void genome_account_record(ipcr_genome *g, uint64_t len, uint64_t cols) { // a r
     g->flags_valid = false;
 }
 
+// ---- exception runs
+bool exc_active(const ipcr_genome *g) { return g->exc_capture && !g->exc_dropped; }
+
+void exc_drop(ipcr_genome *g) { // more runs than the bound: loads and scans go on, the exact read is unsupported
+    if (g->d_exc) (void)hipFree(g->d_exc);
+    g->d_exc = nullptr;
+    g->exc_cap = g->exc_known = g->exc_sorted = 0;
+    g->exc_dropped = true;
+    g->exc_dirty = false;
+    g->exc_host.clear();
+    g->exc_host.shrink_to_fit();
+    g->exc_redo.clear();
+}
+
+// a capturing launch was enqueued on the genome's stream: queue the count's read-back (the caller's wait covers it) and keep
+// the launch, to repeat it if the store overflowed.  Its source bytes must stay in place until exc_settle.
+ipcr_status exc_launched(ipcr_genome *g, std::function<hipError_t(uint64_t cap)> redo) {
+    HIPCHK(hipMemcpyAsync(g->h_exc_count, g->d_exc_count, 8, hipMemcpyDeviceToHost, g->stream));
+    g->exc_redo.push_back(std::move(redo));
+    return IPCR_OK;
+}
+
+// after a wait on the genome's stream that covers every launch in exc_redo: accept their runs, or grow the store, reset the
+// counter to its value before them and repeat them (tile, column-mask and flag writes are idempotent)
+ipcr_status exc_settle(ipcr_genome *g) {
+    if (g->exc_redo.empty() || !exc_active(g)) { g->exc_redo.clear(); return IPCR_OK; }
+    for (int round = 0; round < 4; ++round) {
+        const uint64_t v = *g->h_exc_count;
+        if (v <= g->exc_cap) {
+            g->exc_dirty |= v != g->exc_known;
+            g->exc_known = v;
+            g->exc_redo.clear();
+            return IPCR_OK;
+        }
+        if (v + g->exc_host.size() > g->exc_bound) { exc_drop(g); return IPCR_OK; }
+        uint64_t cap = g->exc_cap;
+        if (cap == 0) {
+            const char *e = getenv("IPCR_TEST_EXCEPTION_CAP");
+            cap = (e && *e) ? std::max<uint64_t>(1, strtoull(e, nullptr, 10)) : 4096;
+        }
+        while (cap < v) cap *= 2;
+        cap = std::min(cap, std::max(g->exc_bound, v));
+        ipcr_exc_run *nb = nullptr;
+        HIPCHK(hipMalloc((void **)&nb, cap * sizeof(ipcr_exc_run)));
+        if (g->exc_known) HIPCHK(hipMemcpyAsync(nb, g->d_exc, g->exc_known * sizeof(ipcr_exc_run), hipMemcpyDeviceToDevice, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+        if (g->d_exc) (void)hipFree(g->d_exc);
+        g->d_exc = nb;
+        g->exc_cap = cap;
+        *g->h_exc_count = g->exc_known;
+        HIPCHK(hipMemcpyAsync(g->d_exc_count, g->h_exc_count, 8, hipMemcpyHostToDevice, g->stream));
+        for (auto &f : g->exc_redo) HIPCHK(f(cap));
+        HIPCHK(hipMemcpyAsync(g->h_exc_count, g->d_exc_count, 8, hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+    }
+    return fail(IPCR_ERR_DEVICE, "exception runs: the repeated pack launches disagree on their count");
+}
+
+// sort, merge and upload: the read's list is d_exc[0, exc_sorted)
+ipcr_status exc_finalize(ipcr_genome *g) {
+    if (!exc_active(g) || (!g->exc_dirty && g->exc_host.empty())) return IPCR_OK;
+    std::vector<ipcr_exc_run> all(g->exc_known);
+    if (!all.empty()) HIPCHK(hipMemcpyAsync(all.data(), g->d_exc, all.size() * sizeof(ipcr_exc_run), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    all.insert(all.end(), g->exc_host.begin(), g->exc_host.end());
+    g->exc_host.clear();
+    std::sort(all.begin(), all.end(), [](const ipcr_exc_run &a, const ipcr_exc_run &b) { return a.pos < b.pos; });
+    size_t n = 0;
+    for (size_t i = 0; i < all.size(); ++i) {
+        if (n && all[n - 1].byte == all[i].byte && all[n - 1].pos + all[n - 1].len == all[i].pos && all[n - 1].len + (uint64_t)all[i].len < (1ull << 32))
+            all[n - 1].len += all[i].len;
+        else all[n++] = all[i];
+    }
+    all.resize(n);
+    if (n > g->exc_bound) { exc_drop(g); return IPCR_OK; }
+    if (n > g->exc_cap) {
+        if (g->d_exc) (void)hipFree(g->d_exc);
+        g->d_exc = nullptr;
+        g->exc_cap = std::max<uint64_t>(n, 4096);
+        HIPCHK(hipMalloc((void **)&g->d_exc, g->exc_cap * sizeof(ipcr_exc_run)));
+    }
+    *g->h_exc_count = n;
+    if (n) HIPCHK(hipMemcpyAsync(g->d_exc, all.data(), n * sizeof(ipcr_exc_run), hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(g->d_exc_count, g->h_exc_count, 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    g->exc_known = g->exc_sorted = n;
+    g->exc_dirty = false;
+    return IPCR_OK;
+}
+
+// exception runs of host bytes (record bytes seq[0, n) at padded position P0, appended in order), driven by a linear reset-bit plane (hostpack.cpp: bit i of word w = base 32 w + i, set for a byte outside
+// ACGTacgt): only the flagged bases are looked at, so the N runs of an assembly cost one load each, not a pass over the text
+void exc_scan_bits(const uint8_t *seq, uint64_t n, const uint32_t *bits, uint64_t P0, std::vector<ipcr_exc_run> &out) {
+    for (uint64_t w = 0; w * 32u < n; ++w)
+        for (uint32_t x = bits[w]; x; x &= x - 1u) {
+            const uint64_t j = w * 32u + (uint64_t)__builtin_ctz(x);
+            if (j >= n) break;
+            const uint8_t b = seq[j];
+            if (b == 'N') continue;
+            if (!out.empty() && out.back().byte == b && out.back().pos + out.back().len == P0 + j && out.back().len < 0xFFFFFFFFu) ++out.back().len;
+            else { ipcr_exc_run r{}; r.pos = P0 + j; r.len = 1; r.byte = b; out.push_back(r); }
+        }
+}
+
 // ext_flag: where the record's reset-byte flag goes instead of d_flags (the chunk path keeps it in pinned host memory);
 // with it the pack kernel also writes the record's start / length into the device tables (no copy operations)
 ipcr_status genome_add_device(ipcr_genome *g, const uint8_t *dseq, uint64_t len, bool wait = true, uint32_t *ext_flag = nullptr) {
@@ -1178,12 +1320,25 @@ ipcr_status genome_add_device(ipcr_genome *g, const uint8_t *dseq, uint64_t len,
     if ((reinterpret_cast<uintptr_t>(dseq) & 15u) != 0) return fail(IPCR_ERR_INVALID, "device sequence pointer must be 16-byte aligned");
     const uint32_t rec = (uint32_t)g->rec_start.size();
     if (ext_flag) HIPCHK(ipcr::launch_pack(g->stream, dseq, len, g->next_col, cols, g->planes, g->rst, g->d_colmask, ext_flag, g->d_rec_start + rec, g->d_rec_len + rec, g->e0, g->e1));
-    else HIPCHK(ipcr::launch_pack(g->stream, dseq, len, g->next_col, cols, g->planes, g->rst, g->d_colmask, g->d_flags + rec, nullptr, nullptr, g->e0, g->e1));
+    else if (!exc_active(g)) HIPCHK(ipcr::launch_pack(g->stream, dseq, len, g->next_col, cols, g->planes, g->rst, g->d_colmask, g->d_flags + rec, nullptr, nullptr, g->e0, g->e1));
+    else {
+        HIPCHK(ipcr::launch_pack(g->stream, dseq, len, g->next_col, cols, g->planes, g->rst, g->d_colmask, g->d_flags + rec, nullptr, nullptr, g->e0, g->e1,
+                                 g->d_exc, g->exc_cap, g->d_exc_count));
+        const uint64_t col0 = g->next_col;
+        const ipcr_status es = exc_launched(g, [g, dseq, len, col0, cols, rec](uint64_t cap) {
+            return ipcr::launch_pack(g->stream, dseq, len, col0, cols, g->planes, g->rst, g->d_colmask, g->d_flags + rec, nullptr, nullptr, nullptr, nullptr,
+                                     g->d_exc, cap, g->d_exc_count);
+        });
+        if (es != IPCR_OK) return es;
+    }
     if (wait) {
         HIPCHK(hipEventSynchronize(g->e1));
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, g->e0, g->e1));
         g->pack_ms += ms;
+        HIPCHK(hipStreamSynchronize(g->stream)); // (the count's read-back behind the kernel)
+        const ipcr_status es = exc_settle(g);
+        if (es != IPCR_OK) return es;
     }
     genome_account_record(g, len, cols);
     return IPCR_OK;
@@ -1212,8 +1367,19 @@ ipcr_status genome_add_device_batch(ipcr_genome *g, const uint8_t *dbase, const 
     uint32_t *d_prefix = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_tmp) + ((n * sizeof(ipcr_pack_rec) + 15) & ~(size_t)15));
     HIPCHK(hipMemcpyAsync(d_recs, recs.data(), n * sizeof(ipcr_pack_rec), hipMemcpyHostToDevice, g->stream));
     HIPCHK(hipMemcpyAsync(d_prefix, prefix.data(), (n + 1) * 4, hipMemcpyHostToDevice, g->stream));
-    HIPCHK(ipcr::launch_pack_batch(g->stream, dbase, d_recs, d_prefix, (uint32_t)n, prefix[n], g->planes, g->rst, g->d_colmask, g->d_flags));
+    if (!exc_active(g)) HIPCHK(ipcr::launch_pack_batch(g->stream, dbase, d_recs, d_prefix, (uint32_t)n, prefix[n], g->planes, g->rst, g->d_colmask, g->d_flags));
+    else {
+        HIPCHK(ipcr::launch_pack_batch(g->stream, dbase, d_recs, d_prefix, (uint32_t)n, prefix[n], g->planes, g->rst, g->d_colmask, g->d_flags,
+                                       g->d_exc, g->exc_cap, g->d_exc_count));
+        const uint64_t pairs = prefix[n];
+        const ipcr_status es = exc_launched(g, [g, dbase, d_recs, d_prefix, n, pairs](uint64_t cap) {
+            return ipcr::launch_pack_batch(g->stream, dbase, d_recs, d_prefix, (uint32_t)n, pairs, g->planes, g->rst, g->d_colmask, g->d_flags,
+                                           g->d_exc, cap, g->d_exc_count);
+        });
+        if (es != IPCR_OK) return es;
+    }
     HIPCHK(hipStreamSynchronize(g->stream)); // recs / prefix are host vectors of this call
+    { const ipcr_status es = exc_settle(g); if (es != IPCR_OK) return es; } // (dbase and the device tables are still in place)
     for (size_t i = 0; i < n; ++i) {
         g->rec_start.push_back(recs[i].col0 * IPCR_COLUMN_BASES);
         g->rec_len.push_back(lens[i]);
@@ -1273,7 +1439,8 @@ ipcr_status genome_finalize(ipcr_genome *g) {
     } else {
         HIPCHK(hipStreamSynchronize(g->stream));
     }
-    return IPCR_OK;
+    { const ipcr_status es = exc_settle(g); if (es != IPCR_OK) return es; }
+    return exc_finalize(g);
 }
 
 // chunk path (one record, the scratch's own stream): same preparation without waiting for anything; the
@@ -1375,13 +1542,17 @@ static bool genome_add_host_packed(ipcr_genome *g, const uint8_t *seq, uint64_t 
         const uint64_t per = std::max<uint64_t>(8, ((nc + nthreads - 1) / nthreads + 7) / 8 * 8);
         const size_t nitems = (size_t)((nc + per - 1) / per);
         std::vector<uint32_t> iflags(nitems, 0);
+        std::vector<std::vector<ipcr_exc_run>> iruns(exc_active(g) ? nitems : 0);
         uint32_t *dlo = reinterpret_cast<uint32_t *>(g->staging), *hiv = reinterpret_cast<uint32_t *>(g->h_planes);
         // (the previous group's kernel has read the staging buffer and its DMA the pinned planes: in order on the stream, waited for below)
         PackPool::get().run(nitems, [&](size_t k) {
             const uint64_t a = (uint64_t)k * per, n = std::min(per, nc - a), b0 = (c0 + a) * IPCR_COLUMN_BASES;
             const uint64_t nb = b0 < len ? std::min<uint64_t>(len - b0, n * IPCR_COLUMN_BASES) : 0;
             iflags[k] = ipcr::pack_linear(seq + (nb ? b0 : 0), nb, n * IPCR_COLUMN_BASES, dlo + a * 128u, dlo + W + a * 128u, hiv + a * 128u, hiv + W + a * 128u);
+            if (!iruns.empty() && (iflags[k] & 1u)) exc_scan_bits(seq + b0, nb, hiv + W + a * 128u, col0 * IPCR_COLUMN_BASES + b0, iruns[k]); // (only items with a reset byte)
         }, slot_phys(g->device));
+        for (auto &v : iruns) g->exc_host.insert(g->exc_host.end(), v.begin(), v.end());
+        if (exc_active(g) && g->exc_host.size() + g->exc_known > g->exc_bound) exc_drop(g);
         uint32_t fl = 0;
         for (uint32_t f : iflags) fl |= f;
         flags_all |= fl;
@@ -1488,14 +1659,35 @@ ipcr_status ipcr_internal_genome_add_fasta_hostpacked(ipcr_genome *g, const char
                     spans.push_back({r, c0, std::min(GROUP, cols[r] - c0)});
                     rec_dirty[r] = 1;
                 }
+        // exception runs of the dirty groups, from the text (normalised as the device loader does: a-z upper-cased)
+        std::vector<std::vector<ipcr_exc_run>> sruns(exc_active(g) ? spans.size() : 0);
         if (!spans.empty())
             PackPool::get().run(spans.size(), [&](size_t i) {
                 const Span &sp = spans[i];
                 const uint64_t *src = fs.h_iv + word0[sp.r];
                 uint64_t *dst = fs.d_iv + word0[sp.r];
+                const ipcr::FastaRecord &fr = t.records[sp.r];
+                const uint64_t P0 = (g->next_col + (word0[sp.r] / 64u)) * IPCR_COLUMN_BASES;
                 for (uint64_t c = sp.c0; c < sp.c0 + sp.nc; ++c) { // (a group is 256 columns = 8 whole bitmap words: no word is shared)
                     uint64_t any = 0;
                     for (uint32_t k = 0; k < 64u; ++k) any |= src[c * 64u + k];
+                    if (any && !sruns.empty()) // exception runs: only the invalid bases' text bytes are looked at (normalised: a-z upper-cased)
+                        for (uint32_t k = 0; k < 64u; ++k) {
+                            const uint64_t bw = (c * 64u + k) * 64u, ln0 = fr.W ? bw / fr.W : 0, cc0 = fr.W ? bw % fr.W : 0;
+                            for (uint64_t x = src[c * 64u + k]; x; x &= x - 1u) {
+                                const uint32_t bit = (uint32_t)__builtin_ctzll(x);
+                                const uint64_t b = bw + bit;
+                                if (b >= fr.len) break;
+                                uint64_t ln = ln0, cc = cc0 + bit;
+                                while (cc >= fr.W) { cc -= fr.W; ++ln; }
+                                uint8_t ch = t.data[fr.region + ln * (fr.W + fr.lt) + cc];
+                                if (ch >= 'a' && ch <= 'z') ch = (uint8_t)(ch - 32);
+                                if (ch == 'N') continue;
+                                std::vector<ipcr_exc_run> &out = sruns[i];
+                                if (!out.empty() && out.back().byte == ch && out.back().pos + out.back().len == P0 + b && out.back().len < 0xFFFFFFFFu) ++out.back().len;
+                                else { ipcr_exc_run r{}; r.pos = P0 + b; r.len = 1; r.byte = ch; out.push_back(r); }
+                            }
+                        }
                     if (any) {
                         bits[(size_t)bit0[sp.r] + (size_t)(c >> 5)] |= 1u << (c & 31u);
                         bar_copy(reinterpret_cast<uint8_t *>(dst + c * 64u), reinterpret_cast<const uint8_t *>(src + c * 64u), 512u);
@@ -1505,6 +1697,8 @@ ipcr_status ipcr_internal_genome_add_fasta_hostpacked(ipcr_genome *g, const char
         for (size_t r = 0; r < t.records.size(); ++r)
             if (rec_dirty[r])
                 bar_copy(reinterpret_cast<uint8_t *>(fs.d_bits + bit0[r]), reinterpret_cast<const uint8_t *>(bits.data() + bit0[r]), (bit0[r + 1] - bit0[r]) * 4u);
+        for (auto &v : sruns) g->exc_host.insert(g->exc_host.end(), v.begin(), v.end());
+        if (exc_active(g) && g->exc_host.size() + g->exc_known > g->exc_bound) exc_drop(g);
     }
     bar_flush(bi);
     // ---- tiles: one launch per record
@@ -1575,6 +1769,11 @@ ipcr_status ipcr_internal_genome_add_device(ipcr_genome *g, const uint8_t *dseq,
     return st;
 }
 hipStream_t ipcr_internal_genome_stream(ipcr_genome *g) { return g->stream; }
+ipcr_status ipcr_internal_genome_settle(ipcr_genome *g) {
+    if (g->exc_redo.empty()) return IPCR_OK;
+    HIPCHK(hipStreamSynchronize(g->stream));
+    return exc_settle(g);
+}
 int ipcr_internal_genome_phys_device(const ipcr_genome *g) { return slot_phys(g->device); }
 int ipcr_internal_slot_phys(int slot) { return slot_phys(slot); }
 int ipcr_internal_slot_count() { return slot_count(); }
@@ -1613,6 +1812,132 @@ ipcr_status ipcr_genome_read(const ipcr_genome *g, uint32_t record, uint64_t pos
     (void)hipFree(d);
     HIPCHK(e);
     return IPCR_OK;
+}
+
+} // extern "C"
+
+// ipcr_genome_read_windows borrows one of these from a free list (one per concurrent caller ever seen, per device slot, as
+// ProbeCtx): a non-blocking stream and device buffers of fixed size, so the call allocates and frees nothing in steady
+// state, uses no null stream, waits for its own stream only and keeps device memory bounded whatever the output size.
+namespace {
+constexpr uint64_t READ_PIECE_BYTES = 64ull << 20;  // output bytes per gather launch
+constexpr uint64_t READ_PIECE_SEGS = 1ull << 18;    // segments per gather launch
+constexpr uint64_t READ_SEG_BYTES = 16384;          // a longer window is cut into segments of this size (one workgroup each)
+struct ReadCtx {
+    int slot = 0;
+    hipStream_t st = nullptr;
+    uint8_t *d_out = nullptr;
+    ipcr_amp_seg *d_segs = nullptr, *h_segs = nullptr; // h_segs pinned
+};
+std::mutex g_read_mu;
+std::vector<ReadCtx *> g_read_free;
+
+ipcr_status read_ctx_acquire(int slot, ReadCtx **out) {
+    ReadCtx *c = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_read_mu);
+        for (size_t i = 0; i < g_read_free.size(); ++i)
+            if (g_read_free[i]->slot == slot) { c = g_read_free[i]; g_read_free.erase(g_read_free.begin() + (long)i); break; }
+    }
+    if (c) { *out = c; return IPCR_OK; }
+    std::unique_ptr<ReadCtx> n(new ReadCtx);
+    n->slot = slot;
+    hipError_t e = hipStreamCreateWithFlags(&n->st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void **)&n->d_out, READ_PIECE_BYTES);
+    if (e == hipSuccess) e = hipMalloc((void **)&n->d_segs, READ_PIECE_SEGS * sizeof(ipcr_amp_seg));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&n->h_segs, READ_PIECE_SEGS * sizeof(ipcr_amp_seg), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        if (n->d_out) (void)hipFree(n->d_out);
+        if (n->d_segs) (void)hipFree(n->d_segs);
+        if (n->st) (void)hipStreamDestroy(n->st);
+        return fail(IPCR_ERR_DEVICE, "ipcr_genome_read_windows: %s", hipGetErrorString(e));
+    }
+    *out = n.release();
+    return IPCR_OK;
+}
+void read_ctx_release(ReadCtx *c) {
+    std::lock_guard<std::mutex> lk(g_read_mu);
+    g_read_free.push_back(c);
+}
+} // namespace
+
+extern "C" {
+
+ipcr_status ipcr_genome_read_windows(const ipcr_genome *cg, const ipcr_window *windows, int64_t n, uint8_t *out, uint64_t cap,
+                                     uint64_t *offsets, uint64_t *needed) {
+    if (!cg || n < 0 || (n && !windows) || !offsets || !needed) return fail(IPCR_ERR_INVALID, "ipcr_genome_read_windows: null argument");
+    ipcr_genome *g = const_cast<ipcr_genome *>(cg);
+    offsets[0] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const ipcr_window &w = windows[i];
+        if (w.record < 0 || (size_t)w.record >= g->rec_len.size()) return fail(IPCR_ERR_INVALID, "ipcr_genome_read_windows: window %lld: no record %d", (long long)i, w.record);
+        const int64_t L = (int64_t)g->rec_len[(size_t)w.record];
+        if (w.start < 0 || w.end < 0 || w.start > L || w.end > L)
+            return fail(IPCR_ERR_INVALID, "ipcr_genome_read_windows: window %lld [%lld, %lld) outside its record of %lld bases", (long long)i,
+                        (long long)w.start, (long long)w.end, (long long)L);
+        offsets[i + 1] = offsets[i] + (uint64_t)(w.start <= w.end ? w.end - w.start : (L - w.start) + w.end);
+    }
+    *needed = offsets[n];
+    if (cap < *needed) return fail(IPCR_ERR_CAPACITY, "ipcr_genome_read_windows: %llu bytes do not fit %llu", (unsigned long long)*needed, (unsigned long long)cap);
+    DeviceGuard dg(g->device);
+    uint64_t nruns = 0;
+    {
+        std::lock_guard<std::mutex> lk(g->read_mu);
+        const ipcr_status st = genome_finalize(g);
+        if (st != IPCR_OK) return st;
+        if (g->exc_dropped) return fail(IPCR_ERR_UNSUPPORTED, "ipcr_genome_read_windows: the genome holds more than %llu exception runs and keeps none",
+                                        (unsigned long long)g->exc_bound);
+        if (!g->exc_capture) return fail(IPCR_ERR_UNSUPPORTED, "ipcr_genome_read_windows: a scratch-private genome keeps no exception runs");
+        nruns = g->exc_sorted;
+    }
+    if (*needed == 0) return IPCR_OK;
+    if (!out) return fail(IPCR_ERR_INVALID, "ipcr_genome_read_windows: null output");
+    ReadCtx *c = nullptr;
+    ipcr_status st = read_ctx_acquire(g->device, &c);
+    if (st != IPCR_OK) return st;
+    // pieces: consecutive segments whose bytes are consecutive in `out`; a piece is gathered, copied out and waited for
+    uint64_t nseg = 0, piece0 = 0, piece_bytes = 0;
+    auto flush = [&]() -> hipError_t {
+        if (nseg == 0) return hipSuccess;
+        hipError_t e = hipMemcpyAsync(c->d_segs, c->h_segs, nseg * sizeof(ipcr_amp_seg), hipMemcpyHostToDevice, c->st);
+        if (e == hipSuccess) e = ipcr::launch_gather(c->st, g->planes, g->rst, c->d_segs, (uint32_t)nseg, c->d_out, g->d_exc, nruns);
+        if (e == hipSuccess) e = hipMemcpyAsync(out + piece0, c->d_out, piece_bytes, hipMemcpyDeviceToHost, c->st);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->st); // (h_segs and d_out are reused by the next piece)
+        piece0 += piece_bytes;
+        nseg = 0;
+        piece_bytes = 0;
+        return e;
+    };
+    hipError_t e = hipSuccess;
+    for (int64_t i = 0; i < n && e == hipSuccess; ++i) {
+        const ipcr_window &w = windows[i];
+        const uint64_t R = g->rec_start[(size_t)w.record], L = g->rec_len[(size_t)w.record];
+        const uint64_t s0 = (uint64_t)w.start, e0 = (uint64_t)w.end;
+        // the window's pieces in padded coordinates: [R + start, R + end), or [R + start, R + L) ++ [R, R + end)
+        const uint64_t part_p[2] = {R + s0, R}, part_n[2] = {s0 <= e0 ? e0 - s0 : L - s0, s0 <= e0 ? 0 : e0};
+        for (int k = 0; k < 2 && e == hipSuccess; ++k)
+            for (uint64_t a = 0; a < part_n[k] && e == hipSuccess;) {
+                if (nseg == READ_PIECE_SEGS || piece_bytes == READ_PIECE_BYTES) e = flush();
+                if (e != hipSuccess) break;
+                const uint64_t m = std::min({READ_SEG_BYTES, part_n[k] - a, READ_PIECE_BYTES - piece_bytes});
+                c->h_segs[nseg++] = ipcr_amp_seg{part_p[k] + a, m, 0, 0, piece_bytes};
+                piece_bytes += m;
+                a += m;
+            }
+    }
+    if (e == hipSuccess) e = flush();
+    read_ctx_release(c);
+    HIPCHK(e);
+    return IPCR_OK;
+}
+
+uint64_t ipcr_genome_exception_runs(const ipcr_genome *cg) {
+    if (!cg) return 0;
+    ipcr_genome *g = const_cast<ipcr_genome *>(cg);
+    DeviceGuard dg(g->device);
+    std::lock_guard<std::mutex> lk(g->read_mu);
+    if (genome_finalize(g) != IPCR_OK) return 0;
+    return (g->exc_dropped || !g->exc_capture) ? UINT64_MAX : g->exc_sorted;
 }
 
 uint32_t ipcr_genome_num_records(const ipcr_genome *g) { return g ? (uint32_t)g->rec_start.size() : 0; }
@@ -3117,6 +3442,7 @@ ipcr_status ipcr_scan_chunk(const ipcr_panel *p, ipcr_scratch *s, const uint8_t 
         s->chunk = nullptr;
         st = ipcr_genome_create_on((need_cols + (need_cols >> 2)) * IPCR_COLUMN_BASES, 1, s->device, &s->chunk);
         if (st != IPCR_OK) return st;
+        s->chunk->exc_capture = false; // (its caller holds the bytes)
         // the private chunk genome lives on the scratch's stream: copy, pack, sweep and hand-over are one
         // in-order sequence and the host waits once, at the end
         (void)hipStreamDestroy(s->chunk->stream);
@@ -3747,6 +4073,7 @@ ipcr_status ipcr_nested_windows(const ipcr_genome *g, const ipcr_window *windows
         s->nest = nullptr;
         st = ipcr_genome_create_on((cols + (cols >> 2) + 64) * IPCR_COLUMN_BASES, (uint32_t)std::max<size_t>(n + (n >> 2), 16), s->device, &s->nest);
         if (st != IPCR_OK) return st;
+        s->nest->exc_capture = false;
         (void)hipStreamDestroy(s->nest->stream);
         s->nest->stream = s->stream;
         s->nest->shared_stream = true;

@@ -46,11 +46,77 @@ __device__ __forceinline__ uint32_t swar_zero_bytes(uint32_t x) { // 0x80 in eve
     return ~(t | x) & 0x80808080u;
 }
 
+// Exception runs: bytes outside ACGTacgtN, which the tiles cannot restore, as maximal runs of one byte value
+// inside the pair's n bytes (staged in LDS: byte j = record base + j, at padded position P0 + j).  Only waves whose pair holds
+// a reset byte come here.  Lane l counts the runs that start in its 128 bytes, a wave prefix sum numbers them, one
+// device-scope vector atomic reserves the wave's slots.  Slots past exc.cap are not written but still counted: the host
+// sees the count, grows the store and repeats the launch.  Runs cut at a pair edge are merged on the host.
+struct ipcr_exc_sink {
+    ipcr_exc_run *runs;
+    uint64_t cap;
+    unsigned long long *count; // null: capture nothing (scratch-private genomes)
+};
+__device__ __forceinline__ bool exc_byte(uint32_t b) {
+    const uint32_t u = b & 0xDFu;
+    return !(u == 'A' || u == 'C' || u == 'G' || u == 'T') && b != 'N';
+}
+__device__ __forceinline__ void exc_capture(const uint8_t *bytes, uint32_t n, uint64_t P0, uint32_t lane, const ipcr_exc_sink &exc) {
+    // first the lane's 128 bytes a dword at a time (the pack's SWAR test plus an exact 'N' test): a wave whose reset bytes are
+    // all N -- an assembly's gaps -- leaves here after 8 LDS loads per lane (bytes behind the record are staged as 'a')
+    uint32_t seen = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < 8u; ++t) {
+        const uint4 q = reinterpret_cast<const uint4 *>(bytes)[lane * 8u + t];
+        const uint32_t ws[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const uint32_t w = ws[k], u = w & 0xDFDFDFDFu;
+            const uint32_t e = __builtin_amdgcn_perm(0u, 0x47544341u, (u >> 1) & 0x07070707u);
+            seen |= ~(swar_zero_bytes(e ^ u) | swar_zero_bytes(w ^ 0x4E4E4E4Eu)) & 0x80808080u;
+        }
+    }
+    if (__ballot(seen != 0u) == 0ull) return;
+    const uint32_t j0 = lane * 128u, j1 = min(j0 + 128u, n);
+    uint32_t mine = 0, prev = j0 ? bytes[j0 - 1u] : 0x100u;
+    for (uint32_t j = j0; j < j1; ++j) {
+        const uint32_t b = bytes[j];
+        mine += (exc_byte(b) && b != prev) ? 1u : 0u;
+        prev = b;
+    }
+    uint32_t incl = mine; // inclusive prefix sum over the wave
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
+        if (lane >= d) incl += o;
+    }
+    const uint32_t total = (uint32_t)__shfl((int)incl, 63, 64);
+    if (total == 0u) return;
+    unsigned long long first = 0;
+    if (lane == 0u) first = __hip_atomic_fetch_add(exc.count, (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    first = __shfl(first, 0, 64);
+    uint64_t slot = first + (incl - mine);
+    prev = j0 ? bytes[j0 - 1u] : 0x100u;
+    for (uint32_t j = j0; j < j1; ++j) {
+        const uint32_t b = bytes[j];
+        if (exc_byte(b) && b != prev) {
+            uint32_t e = j + 1u;
+            while (e < n && bytes[e] == b) ++e;
+            if (slot < exc.cap) {
+                const uint64_t P = P0 + j;
+                *reinterpret_cast<uint4 *>(exc.runs + slot) = make_uint4((uint32_t)P, (uint32_t)(P >> 32), e - j, b);
+            }
+            ++slot;
+        }
+        prev = b;
+    }
+}
+
 template <bool ALIGNED>
 __device__ __forceinline__ void pack_pair(const uint8_t *__restrict__ seq, uint64_t len, uint64_t col0, uint64_t ncol,
                                           uint64_t pairidx, uint32_t lane, uint32_t *mine,
                                           uint32_t *__restrict__ planes, uint32_t *__restrict__ rst,
-                                          uint64_t *__restrict__ colmask, uint32_t *__restrict__ rec_flags) {
+                                          uint64_t *__restrict__ colmask, uint32_t *__restrict__ rec_flags,
+                                          const ipcr_exc_sink &exc) {
     const uint64_t base = pairidx * 2u * IPCR_COLUMN_BASES; // record-local first base of my column pair
 #pragma unroll
     for (uint32_t it = 0; it < 8u; ++it) {
@@ -109,7 +175,11 @@ __device__ __forceinline__ void pack_pair(const uint8_t *__restrict__ seq, uint6
     const bool saw_rst = (ors[0] | ors[1] | ors[2] | ors[3]) != 0u;
     // bit 0 is the only bit a record's flag word ever gets: a plain store (idempotent, also right when the word lives
     // in pinned host memory, where the chunk path keeps it -- no copy operation brings it back)
-    if (__ballot(saw_rst) != 0ull && lane == 0u) __hip_atomic_store(rec_flags, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (__ballot(saw_rst) != 0ull) {
+        if (lane == 0u) __hip_atomic_store(rec_flags, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (exc.count) exc_capture(reinterpret_cast<const uint8_t *>(mine), len > base ? (uint32_t)min<uint64_t>(len - base, 2u * IPCR_COLUMN_BASES) : 0u,
+                                   col0 * IPCR_COLUMN_BASES + base, lane, exc);
+    }
 }
 
 __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ seq, uint64_t len,
@@ -119,7 +189,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ s
                                                    uint64_t *__restrict__ colmask,
                                                    uint32_t *__restrict__ rec_flags,
                                                    uint64_t *__restrict__ rec_start_out,
-                                                   uint64_t *__restrict__ rec_len_out) {
+                                                   uint64_t *__restrict__ rec_len_out, ipcr_exc_sink exc) {
     __shared__ uint32_t s_in[4][2048]; // per wave: 2 columns x 32 strands x 32 dwords
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     if (rec_start_out && blockIdx.x == 0 && threadIdx.x == 0) { // chunk path: the one record's table entries, no copy operation
@@ -128,7 +198,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ s
     }
     const uint64_t pairidx = (uint64_t)blockIdx.x * 4u + wv;
     if (pairidx * 2u >= ncol) return; // waves are independent (no workgroup barrier)
-    pack_pair<true>(seq, len, col0, ncol, pairidx, lane, s_in[wv], planes, rst, colmask, rec_flags);
+    pack_pair<true>(seq, len, col0, ncol, pairidx, lane, s_in[wv], planes, rst, colmask, rec_flags, exc);
 }
 
 // many records in one launch (a nested-PCR batch or a fragmented assembly has thousands of short records, one launch
@@ -137,7 +207,8 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ s
 __global__ __launch_bounds__(256) void pack_batch_kernel(const uint8_t *__restrict__ base, const ipcr_pack_rec *__restrict__ recs,
                                                          const uint32_t *__restrict__ pair_prefix, uint32_t nrec,
                                                          uint32_t *__restrict__ planes, uint32_t *__restrict__ rst,
-                                                         uint64_t *__restrict__ colmask, uint32_t *__restrict__ rec_flags) {
+                                                         uint64_t *__restrict__ colmask, uint32_t *__restrict__ rec_flags,
+                                                         ipcr_exc_sink exc) {
     __shared__ uint32_t s_in[4][2048];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     const uint64_t gp = (uint64_t)blockIdx.x * 4u + wv;
@@ -148,7 +219,7 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const uint8_t *__restri
         if (pair_prefix[mid] <= gp) lo = mid; else hi = mid;
     }
     const ipcr_pack_rec r = recs[lo];
-    pack_pair<false>(base + r.src_off, r.len, r.col0, r.ncol, gp - pair_prefix[lo], lane, s_in[wv], planes, rst, colmask, rec_flags + r.flag_idx);
+    pack_pair<false>(base + r.src_off, r.len, r.col0, r.ncol, gp - pair_prefix[lo], lane, s_in[wv], planes, rst, colmask, rec_flags + r.flag_idx, exc);
 }
 
 // fill columns [col_begin, col_end) with padding (inv=1, everything else 0)
@@ -618,19 +689,65 @@ __global__ void unpack_kernel(const uint32_t *__restrict__ planes, const uint32_
     out[i] = ch;
 }
 
-// gather amplicons of products: seg[i] = {P_start_a, len_a, P_start_b, len_b, out_offset}
-__global__ void gather_amplicons_kernel(const uint32_t *__restrict__ planes, const uint32_t *__restrict__ rst,
-                                        const ipcr_amp_seg *__restrict__ segs, uint8_t *__restrict__ out) {
+// gather amplicons of products: seg[i] = {P_start_a, len_a, P_start_b, len_b, out_offset}.  A lane decodes four consecutive
+// output bytes and stores them as one dword (byte stores only in a segment's partial first / last dword, which a
+// neighbouring segment may share).  With a run list (ipcr_genome_read_windows), the workgroup then binary-searches the
+// first run of each of its two pieces and overwrites the bytes the runs cover: those bytes decoded as 'N'.
+__device__ __forceinline__ uint8_t gather_base(const uint32_t *__restrict__ planes, const uint32_t *__restrict__ rst, uint64_t P) {
+    const uint32_t g = base_bits(planes, P);
+    if (!(g & 4u)) return (uint8_t)"ACGT"[g & 3u];
+    if (!rst_bit(rst, P)) return (uint8_t)"acgt"[g & 3u];
+    return (uint8_t)'N';
+}
+__device__ __forceinline__ uint64_t exc_first_ending_after(const ipcr_exc_run *__restrict__ runs, uint64_t n, uint64_t P) {
+    uint64_t lo = 0, hi = n; // first run with pos + len > P (runs are sorted and disjoint: their ends are sorted too)
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (runs[mid].pos + runs[mid].len <= P) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(256) void gather_amplicons_kernel(const uint32_t *__restrict__ planes, const uint32_t *__restrict__ rst,
+                                                               const ipcr_amp_seg *__restrict__ segs, uint8_t *__restrict__ out,
+                                                               const ipcr_exc_run *__restrict__ runs, uint64_t nruns) {
     const ipcr_amp_seg s = segs[blockIdx.x];
     const uint64_t total = s.len_a + s.len_b;
-    for (uint64_t i = threadIdx.x; i < total; i += blockDim.x) {
-        const uint64_t P = (i < s.len_a) ? s.pa + i : s.pb + (i - s.len_a);
-        const uint32_t g = base_bits(planes, P);
-        uint8_t ch;
-        if (!(g & 4u)) ch = (uint8_t)"ACGT"[g & 3u];
-        else if (!rst_bit(rst, P)) ch = (uint8_t)"acgt"[g & 3u];
-        else ch = 'N';
-        out[s.out_off + i] = ch;
+    if (total == 0) return;
+    const uint64_t o0 = s.out_off, o1 = s.out_off + total;
+    const uint64_t w0 = o0 & ~(uint64_t)3;
+    for (uint64_t w = w0 + 4u * threadIdx.x; w < o1; w += 4u * blockDim.x) {
+        uint32_t v = 0, have = 0;
+#pragma unroll
+        for (uint32_t t = 0; t < 4u; ++t) {
+            const uint64_t o = w + t;
+            if (o < o0 || o >= o1) continue;
+            const uint64_t i = o - o0;
+            const uint64_t P = (i < s.len_a) ? s.pa + i : s.pb + (i - s.len_a);
+            v |= (uint32_t)gather_base(planes, rst, P) << (8u * t);
+            have |= 1u << t;
+        }
+        if (have == 0xFu) *reinterpret_cast<uint32_t *>(out + w) = v;
+        else
+            for (uint32_t t = 0; t < 4u; ++t)
+                if (have & (1u << t)) out[w + t] = (uint8_t)(v >> (8u * t));
+    }
+    if (nruns == 0) return;
+    __syncthreads(); // (workgroup-scope fence: the overwrites below land after the decoded bytes)
+#pragma unroll
+    for (uint32_t piece = 0; piece < 2u; ++piece) {
+        const uint64_t pa = piece ? s.pb : s.pa, pl = piece ? s.len_b : s.len_a, off = piece ? o0 + s.len_a : o0;
+        if (pl == 0) continue;
+        __shared__ uint64_t s_first;
+        if (threadIdx.x == 0) s_first = exc_first_ending_after(runs, nruns, pa);
+        __syncthreads();
+        const uint64_t k0 = s_first;
+        __syncthreads();
+        for (uint64_t k = k0 + threadIdx.x; k < nruns; k += blockDim.x) {
+            const ipcr_exc_run r = runs[k];
+            if (r.pos >= pa + pl) break;
+            const uint64_t a = max(r.pos, pa), b = min(r.pos + r.len, pa + pl);
+            for (uint64_t P = a; P < b; ++P) out[off + (P - pa)] = r.byte;
+        }
     }
 }
 
@@ -777,13 +894,14 @@ namespace ipcr {
 
 hipError_t launch_pack(hipStream_t st, const uint8_t *seq, uint64_t len, uint64_t col0, uint64_t ncol,
                        uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint32_t *rec_flags, uint64_t *rec_start_out, uint64_t *rec_len_out,
-                       hipEvent_t start, hipEvent_t stop) {
+                       hipEvent_t start, hipEvent_t stop, ipcr_exc_run *exc_runs, uint64_t exc_cap, unsigned long long *exc_count) {
     const uint64_t pairs = (ncol + 1u) / 2u;
     const uint64_t grid = (pairs + 3u) / 4u;
     if (grid == 0) return hipSuccess;
     // start / stop ride on the dispatch itself (its begin and end timestamps): no marker packets around the kernel
     hipExtLaunchKernelGGL(pack_kernel, dim3((uint32_t)grid), dim3(256), 0, st, start, stop, 0,
-                          seq, len, col0, ncol, planes, rst, colmask, rec_flags, rec_start_out, rec_len_out);
+                          seq, len, col0, ncol, planes, rst, colmask, rec_flags, rec_start_out, rec_len_out,
+                          ipcr_exc_sink{exc_runs, exc_cap, exc_count});
     return hipGetLastError();
 }
 
@@ -803,10 +921,12 @@ hipError_t launch_tiles_from_linear(hipStream_t st, const uint32_t *lin_lo, cons
 }
 
 hipError_t launch_pack_batch(hipStream_t st, const uint8_t *base, const ipcr_pack_rec *recs, const uint32_t *pair_prefix,
-                             uint32_t nrec, uint64_t total_pairs, uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint32_t *rec_flags) {
+                             uint32_t nrec, uint64_t total_pairs, uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint32_t *rec_flags,
+                             ipcr_exc_run *exc_runs, uint64_t exc_cap, unsigned long long *exc_count) {
     const uint64_t grid = (total_pairs + 3u) / 4u;
     if (grid == 0 || nrec == 0) return hipSuccess;
-    pack_batch_kernel<<<dim3((uint32_t)grid), dim3(256), 0, st>>>(base, recs, pair_prefix, nrec, planes, rst, colmask, rec_flags);
+    pack_batch_kernel<<<dim3((uint32_t)grid), dim3(256), 0, st>>>(base, recs, pair_prefix, nrec, planes, rst, colmask, rec_flags,
+                                                                   ipcr_exc_sink{exc_runs, exc_cap, exc_count});
     return hipGetLastError();
 }
 
@@ -884,9 +1004,9 @@ hipError_t launch_unpack(hipStream_t st, const uint32_t *planes, const uint32_t 
 }
 
 hipError_t launch_gather(hipStream_t st, const uint32_t *planes, const uint32_t *rst, const ipcr_amp_seg *segs,
-                         uint32_t nseg, uint8_t *out) {
+                         uint32_t nseg, uint8_t *out, const ipcr_exc_run *runs, uint64_t nruns) {
     if (nseg == 0) return hipSuccess;
-    gather_amplicons_kernel<<<dim3(nseg), dim3(256), 0, st>>>(planes, rst, segs, out);
+    gather_amplicons_kernel<<<dim3(nseg), dim3(256), 0, st>>>(planes, rst, segs, out, runs, nruns);
     return hipGetLastError();
 }
 

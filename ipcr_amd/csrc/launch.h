@@ -10,7 +10,9 @@ namespace ipcr {
 hipError_t launch_pack(hipStream_t st, const uint8_t *seq, uint64_t len, uint64_t col0, uint64_t ncol,
                        uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint32_t *rec_flags, uint64_t *rec_start_out = nullptr,
                        uint64_t *rec_len_out = nullptr, // rec_*_out: the kernel also writes the record's table entries (chunk path)
-                       hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+                       hipEvent_t start = nullptr, hipEvent_t stop = nullptr,
+                       // exc_count non-null: capture the record's exception runs into exc_runs[0, exc_cap)
+                       ipcr_exc_run *exc_runs = nullptr, uint64_t exc_cap = 0, unsigned long long *exc_count = nullptr);
 // host-packed linear bit planes (hostpack.cpp) -> tiles; lin_* point at the words of column col0 (the slice's first)
 hipError_t launch_tiles_from_linear(hipStream_t st, const uint32_t *lin_lo, const uint32_t *lin_hi, const uint32_t *lin_iv,
                                     const uint32_t *lin_rs, uint64_t rec_col0, uint64_t col0, uint64_t ncol, uint64_t len,
@@ -21,7 +23,8 @@ uint32_t pack_linear(const uint8_t *seq, uint64_t len, uint64_t padded, uint32_t
 bool pack_linear_is_simd();
 
 hipError_t launch_pack_batch(hipStream_t st, const uint8_t *base, const ipcr_pack_rec *recs, const uint32_t *pair_prefix,
-                             uint32_t nrec, uint64_t total_pairs, uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint32_t *rec_flags);
+                             uint32_t nrec, uint64_t total_pairs, uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint32_t *rec_flags,
+                             ipcr_exc_run *exc_runs = nullptr, uint64_t exc_cap = 0, unsigned long long *exc_count = nullptr);
 hipError_t launch_fill_pad(hipStream_t st, uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint64_t col_begin, uint64_t col_end);
 // flags[i] = does [win[2 i], win[2 i + 1]) (padded genome coordinates) hold a reset byte (win, flags: device memory)
 hipError_t launch_window_reset(hipStream_t st, const uint32_t *rst, const uint64_t *win, uint32_t nwin, uint32_t *flags);
@@ -39,8 +42,9 @@ hipError_t launch_verify(hipStream_t st, const uint32_t *planes, const uint32_t 
                          uint32_t single = 0); // single: every queue entry holds one candidate (bits has one bit set)
 hipError_t launch_unpack(hipStream_t st, const uint32_t *planes, const uint32_t *rst, uint64_t P0, uint64_t n,
                          uint8_t *out);
+// runs: the genome's sorted exception runs (nruns of them) to overwrite the 'N' they decode as; null: tiles only
 hipError_t launch_gather(hipStream_t st, const uint32_t *planes, const uint32_t *rst, const ipcr_amp_seg *segs,
-                         uint32_t nseg, uint8_t *out);
+                         uint32_t nseg, uint8_t *out, const ipcr_exc_run *runs = nullptr, uint64_t nruns = 0);
 hipError_t launch_probe(hipStream_t st, const uint8_t *amps, const uint64_t *amp_off, uint32_t namp,
                         const uint8_t *pmask, const uint8_t *rmask, uint32_t plen, uint32_t max_mm,
                         uint32_t fastpath, ipcr_probe_rec *out,

@@ -334,6 +334,28 @@ class Genome:
         _lib.check(_lib.lib().ipcr_genome_read(self._h, record, pos, buf, length))
         return buf.raw[:length]
 
+    def read_windows(self, windows) -> List[bytes]:
+        """Exact bytes of (record, start, end) windows, as loaded (ipcr_genome_read_windows): record[start:end], or
+        record[start:] + record[:end] when start > end.  One call for all of them."""
+        n = len(windows)
+        arr = (_lib.Window * max(n, 1))()
+        for i, (r, s, e) in enumerate(windows):
+            arr[i].record, arr[i].start, arr[i].end = int(r), int(s), int(e)
+        offs = (C.c_uint64 * (n + 1))()
+        need = C.c_uint64()
+        total = 0
+        for r, s, e in windows:
+            total += (e - s) if s <= e else self.record_len(int(r)) - s + e
+        buf = C.create_string_buffer(max(total, 1))
+        _lib.check(_lib.lib().ipcr_genome_read_windows(self._h, arr, n, buf, max(total, 0), offs, C.byref(need)))
+        raw = buf.raw
+        return [raw[offs[i]:offs[i + 1]] for i in range(n)]
+
+    @property
+    def exception_runs(self) -> int:
+        """Runs of bytes outside ACGTacgtN the genome keeps (2**64 - 1: more than its bound, none kept)."""
+        return int(_lib.lib().ipcr_genome_exception_runs(self._h))
+
     @property
     def num_records(self) -> int:
         return _lib.lib().ipcr_genome_num_records(self._h)

@@ -214,6 +214,22 @@ def readme_text():
                     if cb:
                         parts.append("cpu_baseline %s Gbases/s on %d threads (%s)" % (_num(cb["value"]), cb["cores"], cb["kind"]))
                     row = "; ".join(parts)
+            elif f.endswith(".json") and "_read_windows" in f:  # tools/product_seqs_probe.py
+                j = json.load(open(path))
+                row = "`tools/product_seqs_probe.py`: `ipcr_genome_read_windows` over %d windows of a %s Gb genome (%d exception runs), %d bytes in %s ms = %s GB/s" % (
+                    j["windows"], _num(j["genome_bases"] / 1e9), j["exception_runs"], j["bytes"], _num(j["read_s_min"] * 1e3), _num(j["gb_per_s"]))
+            elif f.endswith(".json") and "_fasta_load_ab" in f:  # tools/fasta_load_exc_ab.py
+                j = json.load(open(path))
+                row = "`tools/fasta_load_exc_ab.py`: FASTA load of %s Gb, median of %d alternating children (ms): %s" % (
+                    _num(j["gbases"]), j["rounds"], ", ".join("%s %s" % (k, _num(v)) for k, v in j["load_ms_median"].items()))
+            if row is None and f.endswith("_stats.csv") and "_read_windows" in f:  # the probe under rocprofv3 --stats
+                with open(path, newline="") as fh:
+                    rows = {r.get("Name", "").split("(")[0]: r for r in csv.DictReader(fh)}
+                for name in ("gather_amplicons_kernel", "MEMORY_COPY_DEVICE_TO_HOST"):
+                    if name in rows:
+                        r = rows[name]
+                        row = "`rocprofv3 --stats`: `%s` %s calls, %s ms in all (average %s us)" % (
+                            name, r["Calls"], _num(float(r["TotalDurationNs"]) / 1e6), _num(float(r["AverageNs"]) / 1e3))
             if row is None:
                 row = "(see the file)"
             out.append("| `%s` | %s |" % (f, row))
