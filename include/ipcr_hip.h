@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define IPCR_ABI_VERSION 4
+#define IPCR_ABI_VERSION 5
 #define IPCR_MAX_PRIMER_LEN 128 /* longest primer/probe the device path accepts */
 #define IPCR_MAX_MM 16          /* largest --mismatches the device path accepts */
 
@@ -449,9 +449,19 @@ ipcr_status ipcr_genome_read_windows(const ipcr_genome *g, const ipcr_window *wi
                                      uint64_t cap, uint64_t *offsets, uint64_t *needed);
 /* runs of bytes outside ACGTacgtN the genome keeps (UINT64_MAX: dropped, see above) */
 uint64_t ipcr_genome_exception_runs(const ipcr_genome *g);
-/* every product of the last scan on `outer` (out[i] <-> product i) */
+/* every product of the last scan on `outer` over the resident genome `g` (out[i] <-> product i).  After
+ * ipcr_scan_genome_chunked the products' window-local coordinates are put back into their records first. */
 ipcr_status ipcr_nested_products(const ipcr_scratch *outer, const ipcr_genome *g, const ipcr_panel *inner,
                                  ipcr_scratch *inner_scratch, ipcr_nested_hit *out, int64_t n_out);
+/* ipcr-nested on a worker: every product of the LAST ipcr_scan_chunk on `outer` (out[i] <-> product i), the amplicons read
+ * from the tiles that call packed (the outer scratch's private chunk genome keeps them until its next scan): chunk-local
+ * [start, end), or chunk[start:] ++ chunk[:end] for a wrap-around product -- what the pipeline slices into Product.Seq on
+ * the worker (internal/pipeline/pipeline.go:80-89).  The inner scan runs on `inner_scratch`'s stream after a host wait for
+ * the outer scratch's stream.  IPCR_ERR_INVALID when the last scan on `outer` was not an ipcr_scan_chunk, when
+ * outer == inner_scratch, when n_out differs from the product count or the scratches live on different devices;
+ * IPCR_ERR_DEVICE for a host-only scratch.  An empty chunk scan returns IPCR_OK and writes nothing. */
+ipcr_status ipcr_nested_scratch_products(const ipcr_scratch *outer, const ipcr_panel *inner, ipcr_scratch *inner_scratch,
+                                         ipcr_nested_hit *out, int64_t n_out);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,8 @@ Only what sits directly either side of the scan path ("nex
 FASTA -> resident tiles, the collector's total product order, and the text/TSV rows -- with the
 reference's flag names and defaults (internal/clibase/common.go:61-110) so outputs can be
 diffed against `ipcr`.  --products (JSONL `seq`) and --output fasta carry the amplicon bytes, read exactly from the
-resident genome (ipcr_genome_read_windows).  Thermo scoring, pretty blocks, JSON and nested PCR are out of scope.
+resident genome (ipcr_genome_read_windows).  Thermo scoring, pretty blocks and JSON are out of scope; nested PCR
+is `ipcr_amd.nested_cli`.
 
     python -m ipcr_amd.cli -f AGAGTTTGATCMTGGCTCAG -r TACGGYTACCTTGTTAYGACTT --mismatches 0 demo.fa
 """
@@ -161,7 +162,11 @@ def format_jsonl(source_file: str, p: engine.Product, seq: str = "") -> str:
         d["seq"] = seq
     if source_file:
         d["source_file"] = source_file
-    text = json.dumps(d, separators=(",", ":"), ensure_ascii=False)
+    return go_json_escape(json.dumps(d, separators=(",", ":"), ensure_ascii=False))
+
+
+def go_json_escape(text: str) -> str:
+    """encoding/json's HTML escaping (the Encoder default) over what json.dumps wrote: <, > and & as \\u escapes"""
     return text.replace("<", "\\u003c").replace(">", "\\u003e").replace("&", "\\u0026")
 
 

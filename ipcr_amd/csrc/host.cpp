@@ -4019,8 +4019,11 @@ ipcr_status ipcr_probe_scratch_products(ipcr_scratch *s, const char *probe, int3
 
 // ------------------------------------------------------------------------------ nested PCR
 
-ipcr_status ipcr_nested_windows(const ipcr_genome *g, const ipcr_window *windows, int64_t n64, const ipcr_panel *inner,
-                                ipcr_scratch *s, ipcr_nested_hit *out) {
+// The one body of the three entry points below: gather the amplicons of `windows` from the tiles of `g` -> ONE batched pack
+// into the inner scratch's private genome -> ONE inner scan -> the best inner product per amplicon.  `g` is a resident
+// genome, or the outer scratch's private chunk genome (ipcr_nested_scratch_products).
+static ipcr_status nested_run(const ipcr_genome *g, const ipcr_window *windows, int64_t n64, const ipcr_panel *inner,
+                              ipcr_scratch *s, ipcr_nested_hit *out) {
     ipcr_status st = scratch_ready(inner, s);
     if (st == IPCR_OK) st = same_device(s, g);
     if (st != IPCR_OK) return st;
@@ -4029,7 +4032,10 @@ ipcr_status ipcr_nested_windows(const ipcr_genome *g, const ipcr_window *windows
     const size_t n = (size_t)n64;
     if (n == 0) return IPCR_OK;
     memset(out, 0, n * sizeof *out);
-    st = genome_finalize(const_cast<ipcr_genome *>(g)); // the gather below reads the tiles: padding and packing must be complete
+    // The gather below reads the tiles on THIS scratch's stream.  genome_finalize waits on the host for the genome's own stream:
+    // a resident genome's loads, or -- for a chunk genome, whose stream is the outer scratch's -- the outer pack and sweep.
+    // (The outer scan's collection has already waited for that stream; this wait is what orders the two streams here.)
+    st = genome_finalize(const_cast<ipcr_genome *>(g)); // padding and packing must be complete
     if (st != IPCR_OK) return st;
     // amplicon = record[start:end], or record[start:] ++ record[:end] for wrap-around products
     // (internal/pipeline/pipeline.go:80-89); every amplicon starts 16-byte aligned (pack kernel input)
@@ -4113,20 +4119,60 @@ ipcr_status ipcr_nested_windows(const ipcr_genome *g, const ipcr_window *windows
     return IPCR_OK;
 }
 
+ipcr_status ipcr_nested_windows(const ipcr_genome *g, const ipcr_window *windows, int64_t n, const ipcr_panel *inner,
+                                ipcr_scratch *s, ipcr_nested_hit *out) {
+    return nested_run(g, windows, n, inner, s, out);
+}
+
+// the products of the last scan on `outer` as windows of the genome their amplicons lie in
+static std::vector<ipcr_window> outer_windows(const ipcr_scratch *outer, bool in_windows) {
+    const size_t n = outer->products.size();
+    std::vector<ipcr_window> w(n);
+    for (size_t i = 0; i < n; ++i) {
+        const ipcr_product &pr = outer->products[i];
+        w[i].start = pr.start;
+        w[i].end = pr.end;
+        w[i].record = pr.record;
+        w[i].reserved = 0;
+        // products of ipcr_scan_genome_chunked: `record` is a window, coordinates are window-local (as probe_begin puts them back)
+        if (in_windows && pr.record >= 0 && (size_t)pr.record < outer->windows.size()) {
+            const ipcr_chunk_window &cw = outer->windows[(size_t)pr.record];
+            w[i].record = (int32_t)cw.record;
+            w[i].start += (int64_t)cw.start;
+            w[i].end += (int64_t)cw.start;
+        } else if (in_windows) {
+            w[i].record = -1; // (nested_run refuses it: record outside the genome)
+        }
+    }
+    return w;
+}
+
 ipcr_status ipcr_nested_products(const ipcr_scratch *outer, const ipcr_genome *g, const ipcr_panel *inner,
                                  ipcr_scratch *s, ipcr_nested_hit *out, int64_t n_out) {
     if (!outer) return fail(IPCR_ERR_INVALID, "ipcr_nested_products: null argument");
     if (outer == s) return fail(IPCR_ERR_INVALID, "ipcr_nested_products: the inner scan needs a scratch of its own");
     const size_t n = outer->products.size();
     if ((int64_t)n != n_out) return fail(IPCR_ERR_INVALID, "n_out (%lld) != products of the last scan (%zu)", (long long)n_out, n);
-    std::vector<ipcr_window> w(n);
-    for (size_t i = 0; i < n; ++i) {
-        w[i].start = outer->products[i].start;
-        w[i].end = outer->products[i].end;
-        w[i].record = outer->products[i].record;
-        w[i].reserved = 0;
-    }
-    return ipcr_nested_windows(g, w.data(), (int64_t)n, inner, s, out);
+    const std::vector<ipcr_window> w = outer_windows(outer, outer->products_in_windows);
+    return nested_run(g, w.data(), (int64_t)n, inner, s, out);
+}
+
+// ipcr-nested on a worker: the products of the outer scratch's last ipcr_scan_chunk, their amplicons read from the tiles
+// that call packed (the outer scratch's private chunk genome keeps them until its next scan) -- chunk-local [start, end),
+// or chunk[start:] ++ chunk[:end] for a wrap-around product (internal/pipeline/pipeline.go:80-89 slices Product.Seq so)
+ipcr_status ipcr_nested_scratch_products(const ipcr_scratch *outer, const ipcr_panel *inner, ipcr_scratch *s,
+                                         ipcr_nested_hit *out, int64_t n_out) {
+    if (!outer || !s) return fail(IPCR_ERR_INVALID, "ipcr_nested_scratch_products: null argument");
+    if (outer == s) return fail(IPCR_ERR_INVALID, "ipcr_nested_scratch_products: the inner scan needs a scratch of its own");
+    if (!outer->stream || !s->stream) return fail(IPCR_ERR_DEVICE, "host-only scratch: the nested scan has no CPU fallback");
+    if (!outer->last_was_chunk) return fail(IPCR_ERR_INVALID, "ipcr_nested_scratch_products: the outer scratch's last scan was not an ipcr_scan_chunk");
+    const size_t n = outer->products.size();
+    if ((int64_t)n != n_out) return fail(IPCR_ERR_INVALID, "n_out (%lld) != products of the last scan (%zu)", (long long)n_out, n);
+    if (n == 0) return IPCR_OK; // (an empty chunk, or an empty panel's chunk scan, which packs nothing)
+    if (!outer->chunk) return fail(IPCR_ERR_INVALID, "ipcr_nested_scratch_products: the outer scratch holds no chunk");
+    if (outer->device != s->device) return fail(IPCR_ERR_INVALID, "ipcr_nested_scratch_products: scratches of different devices");
+    const std::vector<ipcr_window> w = outer_windows(outer, false);
+    return nested_run(outer->chunk, w.data(), (int64_t)n, inner, s, out);
 }
 
 } // extern "C"

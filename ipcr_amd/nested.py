@@ -61,3 +61,16 @@ def NestedProducts(outer_scratch: engine.SimulationScratch, products: Sequence[e
     _lib.check(_lib.lib().ipcr_nested_products(outer_scratch._h, genome._h, inner._h, inner_scratch._h, out, n))
     res = _convert(out, n, inner, products)
     return [r for r in res if r.InnerFound] if require_inner else res
+
+
+def NestedScratchProducts(outer_scratch: engine.SimulationScratch, products: Sequence[engine.Product],
+                          inner: engine.CompiledPanel, inner_scratch: engine.SimulationScratch,
+                          require_inner: bool = False) -> List[NestedProduct]:
+    """the same for the products of the last ipcr_scan_chunk on `outer_scratch` (SimulateCompiledWithScratch): the worker
+    scans the inner panel over the chunk's own tiles, chunk-local amplicons as pipeline.go:80-89 slices them
+    (ipcr_nested_scratch_products)"""
+    n = len(products)
+    out = (_lib.NestedHit * max(n, 1))()
+    _lib.check(_lib.lib().ipcr_nested_scratch_products(outer_scratch._h, inner._h, inner_scratch._h, out, n))
+    res = _convert(out, n, inner, products)
+    return [r for r in res if r.InnerFound] if require_inner else res

@@ -222,6 +222,24 @@ def readme_text():
                 j = json.load(open(path))
                 row = "`tools/fasta_load_exc_ab.py`: FASTA load of %s Gb, median of %d alternating children (ms): %s" % (
                     _num(j["gbases"]), j["rounds"], ", ".join("%s %s" % (k, _num(v)) for k, v in j["load_ms_median"].items()))
+            elif f.endswith(".json") and "_nested_probe" in f:  # tools/nested_probe.py
+                j = json.load(open(path))
+                r0 = j["reps"][0]
+                row = ("`tools/nested_probe.py`: %s Gb, %d outer products (%d with an inner product, %d amplicon bases); medians: "
+                       "outer ScanGenome %s ms, NestedProducts %s ms, bare ipcr_nested_products %s ms, inner filter %s ms" % (
+                           _num(j["gbases"]), r0["outer_products"], r0["inner_found"], r0["amplicon_bases"], _num(j["median_outer_scan_ms"]),
+                           _num(j["median_nested_products_ms"]), _num(j["median_ipcr_nested_products_call_ms"]), _num(r0["inner_filter_ms"])))
+                if j.get("cli"):
+                    row += "; CLI wall (s): " + ", ".join("%s %s" % (k, _num(v["median_wall_s"])) for k, v in j["cli"].items())
+            elif f.endswith(".json") and "_headline_ab" in f:  # alternating bench runs against the parent build
+                j = json.load(open(path))
+                row = "alternating `%s` runs, C2 Gbases/s: %s" % (j["cmd"], ", ".join("%s %s" % (k, " / ".join(_num(v) for v in vs)) for k, vs in j["headline"].items()))
+            if row is None and f.endswith("_stats.csv") and "_nested" in f:  # the nested probe under rocprofv3 --stats
+                with open(path, newline="") as fh:
+                    rows = {r.get("Name", "").split("(")[0].replace("void ", ""): r for r in csv.DictReader(fh)}
+                row = "`rocprofv3 --kernel-trace --stats`: " + "; ".join("`%s` %s calls, average %s us" % (
+                    name, rows[name]["Calls"], _num(float(rows[name]["AverageNs"]) / 1e3))
+                    for name in ("gather_amplicons_kernel", "pack_batch_kernel", "ipcr_filter", "verify_kernel") if name in rows)
             if row is None and f.endswith("_stats.csv") and "_read_windows" in f:  # the probe under rocprofv3 --stats
                 with open(path, newline="") as fh:
                     rows = {r.get("Name", "").split("(")[0]: r for r in csv.DictReader(fh)}
