@@ -390,16 +390,8 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
         }
         Lmax = std::max<int>(Lmax, p.len);
     }
-    // IPCR_JIT_MERGE=1: ONE rare-branch test per row quad instead of one per row.  The rare branch (some window passed the
-    // block test: exact count, push) reads the window's rows, and the row after a window's last one overwrites its first --
-    // unless the register window has spare slots: with three of them a quad's four rows can all be expanded and tested
-    // before any of their rare branches runs.  W = 24 slots for windows of 17..20 rows (20 more registers, no spill at
-    // two waves per SIMD) buys 15 fewer v_cmp + s_cbranch_vccz pairs per 20 rows.  Needs the peeled loop (no row guards).
-    // MEASURED (3 Gb): C3 0.1958 / 0.1994 ms against 0.1970 / 0.2002 without, C2 0.1806 / 0.1876 against 0.1830 / 0.1815 --
-    // inside the run-to-run spread, for 15 % more generated source (a 24-row loop body): off by default, parity-tested.
     const bool roll = seg || env_int("IPCR_JIT_ROLL", 0, 0, 1) != 0;
-    const bool want_merge = !roll && env_int("IPCR_JIT_PEEL", 1, 0, 1) != 0 && env_int("IPCR_JIT_MERGE", 0, 0, 1) != 0 && Lmax <= 20;
-    const int W = (Lmax + 3 + (want_merge ? 3 : 0)) / 4 * 4; // window rows, multiple of the row-quad (merge: at least three spare)
+    const int W = (Lmax + 3) / 4 * 4; // window rows, multiple of the row-quad
     // tuning knobs; defaults = best of the sweeps on MI355X (tools/sweep_jit.py): windows up to
     // 20 rows leave registers for two quads of prefetch, wider ones spill unless it is one
     const int D = env_int("IPCR_JIT_DEPTH", Lmax <= 20 ? 2 : 1, 1, 4); // row-quads prefetched ahead
@@ -422,7 +414,7 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
     std::vector<Plan> plans;
     for (const auto &p : pats) plans.push_back(choose_plan(p, k, exact_stage));
     // evaluation of every pattern for the window that starts at slot sr
-    auto eval_code = [&](int sr, const std::string &sfx) {
+    auto eval_code = [&](int sr) {
         std::ostringstream o;
         for (size_t q = 0; q < pats.size(); ++q) {
             const Plan &pl = plans[q];
@@ -473,64 +465,50 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
                 for (int i = 0; i < B; ++i) { const std::string e = orchain(pl.blocks[(size_t)i]); o << "            const u32 e" << i << " = " << e << ";\n"; }
                 o << count_code(B, k);
             }
-            o << "            f" << q << sfx << " = f;\n          }\n";
+            o << "            f" << q << " = f;\n          }\n";
         }
         return o.str();
     };
     // The rare branch of a row (some strand of some pattern passed the block test): per pattern the exact count, where the
     // plan has one -- that code names the window's registers, so it exists per (row slot, pattern) -- and then ONE push
-    // site for all patterns: a lane walks the patterns it still has bits for (IPCR_JIT_ONE_PUSH=0: a push per pattern, the
-    // form until round 4 -- three quarters of the generated instructions were those 196 inlined pushes: hiprtc's time is
-    // proportional to the instruction count, 16 300 -> 11 800 for C2).
-    const bool one_push = env_int("IPCR_JIT_ONE_PUSH", 1, 0, 1) != 0;
-    auto rare_code = [&](int sr0, const std::string &cs) {
+    // site for all patterns: a lane walks the patterns it still has bits for.
+    auto rare_code = [&](int sr0) {
         std::ostringstream b;
         for (size_t q = 0; q < pats.size(); ++q) {
             const Plan &pl = plans[q];
             size_t U = 0;
             for (const auto &blk : pl.blocks) U += blk.size();
             const bool exact_already = !pl.counted || pl.blocks.size() == U;
-            const bool refine = !exact_already && exact_stage;
-            if (one_push && !refine) { b << "            const u32 w" << q << " = ~f" << q << cs << ";\n"; continue; }
+            if (exact_already || !exact_stage) { b << "            const u32 w" << q << " = ~f" << q << ";\n"; continue; }
             b << "            u32 w" << q << " = 0u;\n";
-            b << "            if (f" << q << cs << " != 0xFFFFFFFFu) {\n";
-            b << "              u32 f = f" << q << cs << ";\n";
-            if (refine) {
-                b << "              {\n";
-                int e = 0;
-                for (const auto &blk : pl.blocks)
-                    for (int j : blk) b << "            const u32 e" << e++ << " = " << plane_expr(pats[q].mask[j], (sr0 + j) % W, uses_n) << ";\n";
-                b << count_code((int)U, k);
-                b << "              }\n";
-            }
-            if (one_push) b << "              w" << q << " = ~f;\n";
-            else if (offs[q] == 0)
-                b << "              if (f != 0xFFFFFFFFu) push(" << pid(q) << "ull, pos, ~f, lcnt, lkey, lbits, queue, qcap, qcount, counts);\n";
-            else // the window starts offs[q] rows before the filtered part: in the previous strand (= the previous bit) when that crosses row 0
-                b << "              if (f != 0xFFFFFFFFu) { u64 wp = pos; u32 wm = ~f; if (wp >= " << offs[q] << "ull) wp -= " << offs[q]
-                  << "ull; else { wp += " << 128 - offs[q] << "ull; wm >>= 1; } if (wm) push(" << pid(q)
-                  << "ull, wp, wm, lcnt, lkey, lbits, queue, qcap, qcount, counts); }\n";
+            b << "            if (f" << q << " != 0xFFFFFFFFu) {\n";
+            b << "              u32 f = f" << q << ";\n";
+            b << "              {\n";
+            int e = 0;
+            for (const auto &blk : pl.blocks)
+                for (int j : blk) b << "            const u32 e" << e++ << " = " << plane_expr(pats[q].mask[j], (sr0 + j) % W, uses_n) << ";\n";
+            b << count_code((int)U, k);
+            b << "              }\n";
+            b << "              w" << q << " = ~f;\n";
             b << "            }\n";
         }
-        if (one_push) {
-            b << "            u32 pm = 0u";
-            for (size_t q = 0; q < pats.size(); ++q) b << " | (w" << q << " ? " << (1u << q) << "u : 0u)";
-            b << ";\n";
-            b << "            while (pm) { // (lane-divergent: a lane walks the patterns it has surviving strands for)\n"
-                 "              const u32 q = (u32)__builtin_ctz(pm); pm &= pm - 1u;\n"
-                 "              u32 wm = w0;\n";
-            for (size_t q = 1; q < pats.size(); ++q) b << "              if (q == " << q << "u) wm = w" << q << ";\n";
-            // pattern id | rows dropped at the window's start << 16: constants, NOT a table in memory -- a load inside this loop makes
-            // the compiler lose count of the tile loads in flight where the rare path joins the main one (vmcnt(3) for vmcnt(6))
-            b << "              u32 info = " << (pid(0) | ((unsigned)offs[0] << 16)) << "u;\n";
-            for (size_t q = 1; q < pats.size(); ++q) b << "              if (q == " << q << "u) info = " << (pid(q) | ((unsigned)offs[q] << 16)) << "u;\n";
-            b << "              const u32 off = info >> 16;\n"
-                 "              u64 wp = pos;\n"
-                 "              // the window starts `off` rows before the filtered part: in the previous strand (= the previous bit) when that crosses row 0\n"
-                 "              if (off) { if (wp >= (u64)off) wp -= (u64)off; else { wp += (u64)(128u - off); wm >>= 1; } }\n"
-                 "              if (wm) push((u64)(info & 0xFFFFu), wp, wm, lcnt, lkey, lbits, queue, qcap, qcount, counts);\n"
-                 "            }\n";
-        }
+        b << "            u32 pm = 0u";
+        for (size_t q = 0; q < pats.size(); ++q) b << " | (w" << q << " ? " << (1u << q) << "u : 0u)";
+        b << ";\n";
+        b << "            while (pm) { // (lane-divergent: a lane walks the patterns it has surviving strands for)\n"
+             "              const u32 q = (u32)__builtin_ctz(pm); pm &= pm - 1u;\n"
+             "              u32 wm = w0;\n";
+        for (size_t q = 1; q < pats.size(); ++q) b << "              if (q == " << q << "u) wm = w" << q << ";\n";
+        // pattern id | rows dropped at the window's start << 16: constants, NOT a table in memory -- a load inside this loop makes
+        // the compiler lose count of the tile loads in flight where the rare path joins the main one (vmcnt(3) for vmcnt(6))
+        b << "              u32 info = " << (pid(0) | ((unsigned)offs[0] << 16)) << "u;\n";
+        for (size_t q = 1; q < pats.size(); ++q) b << "              if (q == " << q << "u) info = " << (pid(q) | ((unsigned)offs[q] << 16)) << "u;\n";
+        b << "              const u32 off = info >> 16;\n"
+             "              u64 wp = pos;\n"
+             "              // the window starts `off` rows before the filtered part: in the previous strand (= the previous bit) when that crosses row 0\n"
+             "              if (off) { if (wp >= (u64)off) wp -= (u64)off; else { wp += (u64)(128u - off); wm >>= 1; } }\n"
+             "              if (wm) push((u64)(info & 0xFFFFu), wp, wm, lcnt, lkey, lbits, queue, qcap, qcount, counts);\n"
+             "            }\n";
         return b.str();
     };
     // one row step: expand the row into mismatch planes at `slot`, then (if a window ends
@@ -547,7 +525,7 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
         b << "        {\n          u32 ";
         for (size_t q = 0; q < pats.size(); ++q) b << (q ? ", f" : "f") << q;
         b << ";\n";
-        b << eval_code(((slot - LM1) % W + W) % W, "");
+        b << eval_code(((slot - LM1) % W + W) % W);
         b << "          u32 all = f0";
         for (size_t q = 1; q < pats.size(); ++q) b << " & f" << q;
         b << ";\n";
@@ -558,62 +536,8 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
         b << "          if (__builtin_expect(all != 0xFFFFFFFFu, 0)) {\n";
         b << "            const u64 pos = posbase + (u64)(" << xexpr << " - " << LM1 << "u);\n";
         const int sr0 = ((slot - LM1) % W + W) % W;
-        b << rare_code(sr0, "");
+        b << rare_code(sr0);
         b << "          }\n        }\n      }\n";
-        return b.str();
-    };
-    // ---- the merged form: a quad's rows are expanded and tested first (row_head: f<q>_<c>, all_<c>), then ONE branch
-    // covers the rare work of all four (row_rare)
-    auto row_head = [&](int slot, char comp, int c, bool ev) {
-        std::ostringstream b;
-        const std::string sl = std::to_string(slot), cs = "_" + std::to_string(c);
-        b << "      { // window slot " << slot << "\n";
-        b << "        const u32 lo = clo." << comp << ", hi = chi." << comp << ", iv = civ." << comp << ";\n";
-        b << "        a" << sl << " = OR3(lo, hi, iv); c" << sl << " = __builtin_amdgcn_bitop3_b32(lo, hi, iv, 0xEF); g" << sl
-          << " = __builtin_amdgcn_bitop3_b32(lo, hi, iv, 0xFB); t" << sl << " = __builtin_amdgcn_bitop3_b32(lo, hi, iv, 0xBF); n" << sl << " = iv;\n";
-        if (ev) {
-            b << eval_code(((slot - LM1) % W + W) % W, cs);
-            b << "          all" << cs << " = f0" << cs;
-            for (size_t q = 1; q < pats.size(); ++q) b << " & f" << q << cs;
-            b << ";\n";
-        }
-        b << "      }\n";
-        return b.str();
-    };
-    auto row_rare = [&](int slot, int c, const std::string &xexpr) {
-        std::ostringstream b;
-        const std::string cs = "_" + std::to_string(c);
-        b << "          if (all" << cs << " != 0xFFFFFFFFu) {\n";
-        b << "            const u64 pos = posbase + (u64)(" << xexpr << " - " << LM1 << "u);\n";
-        const int sr0 = ((slot - LM1) % W + W) % W;
-        b << rare_code(sr0, cs);
-        b << "          }\n";
-        return b.str();
-    };
-    // the four rows of a quad: slot0 = the first row's slot, xs = each row's number as an expression, ev = is a window of this strand tested there
-    auto quad_rows_merged = [&](int slot0, const std::string xs[4], const bool ev[4]) {
-        std::ostringstream b;
-        int nev = 0;
-        for (int c = 0; c < 4; ++c) nev += ev[c] ? 1 : 0;
-        if (nev) {
-            b << "      u32 ";
-            bool first = true;
-            for (int c = 0; c < 4; ++c) {
-                if (!ev[c]) continue;
-                for (size_t q = 0; q < pats.size(); ++q) { b << (first ? "" : ", ") << "f" << q << "_" << c; first = false; }
-                b << ", all_" << c;
-            }
-            b << ";\n";
-        }
-        for (int c = 0; c < 4; ++c) b << row_head(slot0 + c, "xyzw"[c], c, ev[c]);
-        if (nev) {
-            b << "      {\n        u32 any = ";
-            bool first = true;
-            for (int c = 0; c < 4; ++c) if (ev[c]) { b << (first ? "" : " & ") << "all_" << c; first = false; }
-            b << ";\n        if (__builtin_expect(any != 0xFFFFFFFFu, 0)) {\n";
-            for (int c = 0; c < 4; ++c) if (ev[c]) b << row_rare(slot0 + c, c, xs[c]);
-            b << "        }\n      }\n";
-        }
         return b.str();
     };
     // IPCR_JIT_INVMASK=1 (default): the inv plane of a column that holds no invalid base is all zero (the genome's column
@@ -639,19 +563,12 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
     // bit 31 coming from the neighbour column (lane + 1, or lane 0 of the next block).  The head
     // quads were stashed in LDS when first streamed (each wave its own slice, so no barrier), so
     // nothing is fetched from HBM twice and the neighbour word is just the next lane's LDS slot.
-    // Lane 63's neighbour is column 0 of the NEXT block.  IPCR_JIT_NEIGHBOUR=1 (default): its head words (QW quads x 3
-    // planes) are loaded at the kernel's start, one by each of the first lanes, and kept as a 65th column of the stash --
-    // the wrap quads then read LDS only.  0: lane 63 loads them where they are needed, a divergent branch with three global
-    // loads per wrap quad whose round trip the wave waits for.
-    const bool nb_lds = env_int("IPCR_JIT_NEIGHBOUR", 1, 0, 1) != 0;
+    // Lane 63's neighbour is column 0 of the NEXT block: its head words (QW quads x 3 planes) are loaded at the kernel's
+    // start, one by each of the first lanes, and kept as a 65th column of the stash -- the wrap quads then read LDS only.
     auto load_wrap = [&](int kq) {
         std::ostringstream b;
-        const std::string nl = nb_lds ? "lane + 1u" : "(lane + 1u) & 63u";
-        b << "{ v4 nlo = st[" << kq * 3 << "][" << nl << "], nhi = st[" << kq * 3 + 1 << "][" << nl << "], niv = st["
-          << kq * 3 + 2 << "][" << nl << "];\n";
-        if (!nb_lds)
-        b << "        if (lane == 63u) { nlo = nblk[" << kq * 192 << "]; nhi = nblk[" << kq * 192 + 64 << "]; niv = nblk["
-          << kq * 192 + 128 << "]; }\n";
+        b << "{ v4 nlo = st[" << kq * 3 << "][lane + 1u], nhi = st[" << kq * 3 + 1 << "][lane + 1u], niv = st["
+          << kq * 3 + 2 << "][lane + 1u];\n";
         b << "        p" << D << "lo = (st[" << kq * 3 << "][lane] >> 1) | (nlo << 31); p" << D << "hi = (st[" << kq * 3 + 1
           << "][lane] >> 1) | (nhi << 31); p" << D << "iv = (st[" << kq * 3 + 2 << "][lane] >> 1) | (niv << 31); }";
         return b.str();
@@ -681,10 +598,7 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
     auto load_wrap_dyn = [&](const std::string &kq) { // load_wrap for a quad number known at run time (wave-uniform)
         std::ostringstream b;
         b << "{ const u32 kq = " << kq << ";\n";
-        const std::string nl = nb_lds ? "lane + 1u" : "(lane + 1u) & 63u";
-        b << "        v4 nlo = st[kq * 3u][" << nl << "], nhi = st[kq * 3u + 1u][" << nl << "], niv = st[kq * 3u + 2u][" << nl << "];\n";
-        if (!nb_lds)
-        b << "        if (lane == 63u) { nlo = nblk[kq * 192u]; nhi = nblk[kq * 192u + 64u]; niv = nblk[kq * 192u + 128u]; }\n";
+        b << "        v4 nlo = st[kq * 3u][lane + 1u], nhi = st[kq * 3u + 1u][lane + 1u], niv = st[kq * 3u + 2u][lane + 1u];\n";
         b << "        p" << D << "lo = (st[kq * 3u][lane] >> 1) | (nlo << 31); p" << D << "hi = (st[kq * 3u + 1u][lane] >> 1) | (nhi << 31); p" << D
           << "iv = (st[kq * 3u + 2u][lane] >> 1) | (niv << 31); }";
         return b.str();
@@ -694,7 +608,6 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
     // follows has no "it > 0" test in front of its first LM1 rows and no "it == 0" in front of the stash stores: 19 + 5
     // wave-uniform branches fewer per 20 rows, and straight-line code for the scheduler.
     const bool peel = !roll && NFULL >= 2 && env_int("IPCR_JIT_PEEL", 1, 0, 1) != 0;
-    const bool merge = want_merge && peel && W - Lmax >= 3;
     std::ostringstream pro; // iteration 0 by itself
     for (int u4 = 0; u4 < QPI && peel; ++u4) {
         pro << "  { // quad " << u4 << "\n";
@@ -703,12 +616,6 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
         pro << "      " << load_normal(std::to_string(u4 + D) + "u") << "\n";
         if (u4 < QW)
             pro << "      st[" << u4 * 3 << "][lane] = clo; st[" << u4 * 3 + 1 << "][lane] = chi; st[" << u4 * 3 + 2 << "][lane] = civ;\n";
-        if (merge) {
-            std::string xs[4];
-            bool ev[4];
-            for (int c = 0; c < 4; ++c) { xs[c] = std::to_string(u4 * 4 + c) + "u"; ev[c] = u4 * 4 + c >= LM1; }
-            pro << quad_rows_merged(u4 * 4, xs, ev);
-        } else
         for (int c = 0; c < 4; ++c) {
             const int step = u4 * 4 + c;
             pro << row_code(step, "xyzw"[c], std::to_string(step) + "u", step < LM1 ? "never" : "");
@@ -731,12 +638,6 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
         if (u4 < QW && !peel && !seg)
             body << "      if (it == 0u) { st[" << u4 * 3 << "][lane] = clo; st[" << u4 * 3 + 1 << "][lane] = chi; st[" << u4 * 3 + 2
                  << "][lane] = civ; }\n";
-        if (merge) {
-            std::string xs[4];
-            bool ev[4];
-            for (int c = 0; c < 4; ++c) { xs[c] = "(qi * 4u + " + std::to_string(c) + "u)"; ev[c] = true; }
-            body << quad_rows_merged(u4 * 4, xs, ev);
-        } else
         for (int c = 0; c < 4; ++c) {
             const int step = u4 * 4 + c;
             std::string guard = step < LM1 && !peel ? "it > 0u" : "";
@@ -759,12 +660,6 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
         const int qn = qi + D;
         if (qn < 32) epi << "      " << load_normal(std::to_string(qn) + "u") << "\n";
         else if (qn < QTOTAL) epi << "      " << load_wrap(qn - 32) << "\n";
-        if (merge) {
-            std::string xs[4];
-            bool ev[4];
-            for (int c = 0; c < 4; ++c) { const int x = qi * 4 + c; xs[c] = std::to_string(x) + "u"; ev[c] = x >= LM1 && x < 128 + LM1; }
-            epi << quad_rows_merged((qi % QPI) * 4, xs, ev);
-        } else
         for (int c = 0; c < 4; ++c) {
             const int x = qi * 4 + c;
             const int slot = (qi % QPI) * 4 + c;
@@ -898,31 +793,30 @@ std::string jit_source(const std::vector<ipcr_dev_pattern> &full_pats, int k, un
         s << "a" << i << " = 0, c" << i << " = 0, g" << i << " = 0, t" << i << " = 0, n" << i << " = 0";
     }
     s << ";\n";
-    const int SC = nb_lds ? 65 : 64; // stash columns: the wave's 64 + column 0 of the next block
-    s << "  __shared__ v4 stash[" << WPG << "][" << QW * 3 << "][" << SC << "]; // head quads of each wave's block, for the wrap rows\n";
-    s << "  v4 (*st)[" << SC << "] = stash[wv];\n";
+    // stash columns: the wave's 64 + column 0 of the next block
+    s << "  __shared__ v4 stash[" << WPG << "][" << QW * 3 << "][65]; // head quads of each wave's block, for the wrap rows\n";
+    s << "  v4 (*st)[65] = stash[wv];\n";
     for (int i = 1; i <= D; ++i) {
         const std::string at = seg ? "(seg_f0 * " + std::to_string(QPI) + "u + " + std::to_string(i - 1) + "u) * 192u" : std::to_string((i - 1) * 192);
         const std::string atq = seg ? "seg_f0 * " + std::to_string(QPI) + "u + " + std::to_string(i - 1) + "u" : std::to_string(i - 1) + "u";
         s << "  v4 p" << i << "lo = own[" << at << "], p" << i << "hi = own[" << at << " + 64u], p" << i << "iv = "
           << (invmask ? inv_load(atq, false) : "own[" + at + " + 128u]") << ";\n";
     }
-    if (nb_lds)
-        s << "  v4 nbv = {0u, 0u, 0u, 0u}; // word (lane / 3, lane % 3) of the next block's column 0\n"
-             "  if (lane < " << QW * 3 << "u) nbv = nblk[(lane / 3u) * 192u + (lane % 3u) * 64u];\n";
+    s << "  v4 nbv = {0u, 0u, 0u, 0u}; // word (lane / 3, lane % 3) of the next block's column 0\n"
+         "  if (lane < " << QW * 3 << "u) nbv = nblk[(lane / 3u) * 192u + (lane % 3u) * 64u];\n";
     if (seg) { // the head quads for the wrap rows: loaded by every wave whose walk reaches them (they are in the L2: the block's first wave streams them)
         s << "  if (seg_e1 * " << QPI << "u + " << D << "u > 32u) {\n";
         for (int q = 0; q < QW; ++q)
             s << "    st[" << q * 3 << "][lane] = own[" << q * 192 << "]; st[" << q * 3 + 1 << "][lane] = own[" << q * 192 + 64 << "]; st["
               << q * 3 + 2 << "][lane] = " << (invmask ? inv_load(std::to_string(q) + "u", false) : "own[" + std::to_string(q * 192 + 128) + "]") << ";\n";
-        if (nb_lds) s << "    if (lane < " << QW * 3 << "u) st[lane][64] = nbv;\n";
+        s << "    if (lane < " << QW * 3 << "u) st[lane][64] = nbv;\n";
         s << "  }\n";
     }
     s << pro.str();
-    if (nb_lds && peel) s << "  if (lane < " << QW * 3 << "u) st[lane][64] = nbv; // (loaded before iteration 0: it has long arrived)\n";
+    if (peel) s << "  if (lane < " << QW * 3 << "u) st[lane][64] = nbv; // (loaded before iteration 0: it has long arrived)\n";
     if (seg) s << "  for (u32 it = seg_f0; it < seg_e1; ++it) {\n";
     else s << "  for (u32 it = " << (peel ? 1 : 0) << "u; it < " << NIT << "u; ++it) {\n";
-    if (nb_lds && !peel && !seg) s << "    if (it == 1u && lane < " << QW * 3 << "u) st[lane][64] = nbv;\n";
+    if (!peel && !seg) s << "    if (it == 1u && lane < " << QW * 3 << "u) st[lane][64] = nbv;\n";
     s << body.str() << "  }\n";
     s << epi.str();
     // ---- exact verification of this wave's survivors (verifyAt, core/engine/ac.go:186-213 / the
@@ -1343,28 +1237,11 @@ static unsigned index_words64(const std::vector<ipcr_index_shape> &shapes) {
     for (const ipcr_index_shape &x : shapes) t += ipcr_index_words64(x);
     return t;
 }
-static bool index_paired(const std::vector<ipcr_index_shape> &shapes) { return !shapes.empty() && shapes[0].paired != 0; } // all of a panel's shapes or none
 static unsigned index_image_bytes(const std::vector<ipcr_index_shape> &shapes) { // bitmaps + rank prefixes (uint16 per 64 keys) + first entries + shape constants (build_index)
-    const unsigned per64 = index_paired(shapes) ? 9u : 10u; // two-step tables: 64 keys are four 32-bit words, half of each a copy for the other step
-    const unsigned image = index_words64(shapes) * per64 + (unsigned)shapes.size() * 16u + 32u; // (+ the drain's bit table)
+    const unsigned image = index_words64(shapes) * 10u + (unsigned)shapes.size() * 16u + 32u; // (+ the drain's bit table)
     return (image + 15u) & ~15u;
 }
 unsigned jit_index_image_bytes(const std::vector<ipcr_index_shape> &shapes) { return index_image_bytes(shapes); }
-// Two steps per lookup: steps per queue entry and entry layout for n shapes and windows that reach TR bases back (0: not possible)
-static unsigned paired_plan(size_t ns, int TR, unsigned *mode_out) {
-    const unsigned ROWB = 7;
-    for (unsigned spe : {4u, 2u}) {
-        if (ns * spe > 31u) continue; // payload bits 0..30, one per (shape, step)
-        const unsigned nb = (unsigned)(TR < 0 ? 0 : TR) + spe;
-        if (2u * nb + 6u + ROWB <= 64u) { if (mode_out) *mode_out = 0; return spe; }
-        if (2u * nb + ROWB <= 64u && nb + 6u <= 32u) { if (mode_out) *mode_out = 1; return spe; }
-    }
-    return 0;
-}
-bool jit_index_pairable(size_t n_shapes, int tail_rows) {
-    if (env_int("IPCR_INDEX_TWO_STEP", 0, 0, 1) == 0 || n_shapes == 0) return false; // off unless asked for: measured 18 % SLOWER (below)
-    return paired_plan(n_shapes, tail_rows, nullptr) != 0;
-}
 static unsigned index_queue_entries(const std::vector<ipcr_index_shape> &shapes) { // per-wave hit queue: what the image leaves of the 160 KiB, in rounds of 64
     const unsigned left = 160u * 1024u - std::min(160u * 1024u, index_image_bytes(shapes));
     unsigned q = left / (IPCR_INDEX_WAVES * 16u) / 64u * 64u;
@@ -1432,56 +1309,27 @@ std::string jit_index_source(const std::vector<ipcr_index_shape> &shapes, const 
     for (const Pack &p : packs) byte_layout |= p.sh.size() > 1;
     const unsigned ROWB = 7; // rows 0..127 of the unit
     unsigned SPE = 1, mode = 2;
-    // ---- two steps per lookup (all shapes "3 protected bases + 5 block bases", host.cpp: build_index decides).  The keys of
-    // steps t and t + 1 share two of their three protected bases and four of their five block bases: those twelve bits are
-    // the ADDRESS of a 32-bit word; the base only step t has (the oldest of either field, four bits) picks one of its low 16
-    // bits, the base only step t + 1 has (the newest of either field) one of its high 16 -- ONE ds_read_b32 per shape for
-    // two base steps instead of two ds_read_u8; a shape's table is as large as a 17-bit bitmap: 16 KiB.
-    // MEASURED (C4, 3 Gb): 6.09 ms per sweep against 5.15 with the same 16-bit keys looked up one step at a time (4.99 with
-    // the default 17-bit keys) -- half the LDS lookups and the sweep is 18 % SLOWER.  What the pair saves in addresses
-    // (3 per step instead of 6) it pays twice over in bit indices (one per shape and step, where a pack of byte lookups
-    // shares ONE shift): +10 % VALU instructions, most of them four-cycle v_alignbit.  Splitting the bit collection over
-    // 1 / 2 / 4 / 8 registers changes nothing (6.09 / 6.10 / 6.18 / 6.23): no latency chain -- the sweep follows the VALU
-    // issue count, not the LDS instruction count.  Off by default (IPCR_INDEX_TWO_STEP=1), parity-tested.
-    const bool paired = index_paired(shapes);
-    if (paired) {
-        SPE = paired_plan(NS, TR, &mode);
-        if (SPE == 0) return std::string(); // (build_index asked jit_index_pairable first)
-    } else {
-        const unsigned SH0 = (unsigned)packs.size();
-        unsigned want = byte_layout ? (SH0 <= 2 ? 4u : (SH0 <= 4 ? 2u : 1u)) : (SH0 * 4u <= 31u ? 4u : (SH0 * 2u <= 31u ? 2u : 1u));
-        want = (unsigned)env_int("IPCR_INDEX_STEPS_PER_ENTRY", (int)want, 1, (int)want);
-        while (want & (want - 1u)) --want;
-        for (unsigned spe = want; spe >= 1; spe >>= 1) {
-            const unsigned nb = (unsigned)TR + spe;
-            unsigned top = 0; // highest payload bit: bit 31 is the chain flag
-            for (unsigned p = 0; p < packs.size(); ++p) top = std::max(top, (byte_layout ? 8u * ((unsigned)packs[p].sh.size() - 1u) : 0u) + p + SH0 * (spe - 1u));
-            if (top > 30u) continue;
-            if (2u * nb + 6u + ROWB <= 64u) { SPE = spe; mode = 0; break; }
-            if (2u * nb + ROWB <= 64u && nb + 6u <= 32u) { SPE = spe; mode = 1; break; }
-        }
-        if (mode == 2) { // long primers: the whole k-mer and all its flags are needed
-            SPE = 1;
-            if (byte_layout) { make_packs(false); byte_layout = false; }
-        }
+    const unsigned SH0 = (unsigned)packs.size();
+    unsigned want = byte_layout ? (SH0 <= 2 ? 4u : (SH0 <= 4 ? 2u : 1u)) : (SH0 * 4u <= 31u ? 4u : (SH0 * 2u <= 31u ? 2u : 1u));
+    want = (unsigned)env_int("IPCR_INDEX_STEPS_PER_ENTRY", (int)want, 1, (int)want);
+    while (want & (want - 1u)) --want;
+    for (unsigned spe = want; spe >= 1; spe >>= 1) {
+        const unsigned nb = (unsigned)TR + spe;
+        unsigned top = 0; // highest payload bit: bit 31 is the chain flag
+        for (unsigned p = 0; p < packs.size(); ++p) top = std::max(top, (byte_layout ? 8u * ((unsigned)packs[p].sh.size() - 1u) : 0u) + p + SH0 * (spe - 1u));
+        if (top > 30u) continue;
+        if (2u * nb + 6u + ROWB <= 64u) { SPE = spe; mode = 0; break; }
+        if (2u * nb + ROWB <= 64u && nb + 6u <= 32u) { SPE = spe; mode = 1; break; }
+    }
+    if (mode == 2) { // long primers: the whole k-mer and all its flags are needed
+        SPE = 1;
+        if (byte_layout) { make_packs(false); byte_layout = false; }
     }
     const unsigned NPK = (unsigned)packs.size(), SHF = NPK;
     const unsigned NBAS = (unsigned)TR + SPE;
     const unsigned KMHI = 2u * NBAS > 32u ? 2u * NBAS - 32u : 0u;
     auto bitpos = [&](unsigned p, unsigned i, unsigned j) { return (byte_layout ? 8u * i : 0u) + p + SHF * j; };
     std::vector<int> tab(32, 0);
-    // the tests of a block shift their bits into NCH registers in turn (one chain of 24 dependent shifts is latency, not work)
-    unsigned NCH = paired ? (unsigned)env_int("IPCR_INDEX_ACC_CHAINS", 1, 1, 8) : 1u;
-    while (paired && ((unsigned)NS * SPE) % NCH) --NCH;
-    const unsigned NPC = paired ? (unsigned)NS * SPE / NCH : 0u; // tests per chain
-    const bool use_add = env_int("IPCR_INDEX_ACC_ADD", 0, 0, 1) != 0; // dev knob: a chain grows by add + v_bitop3 (from bit 0 up) instead of one v_alignbit (from bit 31 down)
-    if (paired) { // the c-th (shape, step) test of an entry's block, in the order the code below makes them -> payload bit (c % NCH) * NPC + c / NCH
-        unsigned c = 0;
-        for (unsigned pi = 0; pi < SPE / 2u; ++pi)
-            for (const Grp &g : groups)
-                for (int si : g.sh)
-                    for (unsigned o = 0; o < 2u; ++o, ++c) tab[(c % NCH) * NPC + (use_add ? NPC - 1u - c / NCH : c / NCH)] = si | (int)((SPE - 1u - (2u * pi + o)) << 4);
-    } else
     for (unsigned p = 0; p < NPK; ++p)
         for (unsigned i = 0; i < packs[p].sh.size(); ++i)
             for (unsigned j = 0; j < SPE; ++j) tab[bitpos(p, i, j)] = packs[p].sh[i] | (int)(j << 4);
@@ -1491,7 +1339,7 @@ std::string jit_index_source(const std::vector<ipcr_index_shape> &shapes, const 
 
     std::ostringstream s;
     s << "// generated by ipcr_amd/csrc/jit.cpp: seed-index filter (transposed k-mers), " << NS << " key shapes in " << groups.size() << " groups / " << NPK
-      << " packs, 128 rows per strand, " << SPE << " steps per queue entry (entry layout " << "ABC"[mode] << ")" << (paired ? ", two steps per lookup" : "") << "\n";
+      << " packs, 128 rows per strand, " << SPE << " steps per queue entry (entry layout " << "ABC"[mode] << ")\n";
     s << "#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n";
     s << "typedef unsigned int u32;\ntypedef unsigned long long u64;\ntypedef long long i64;\n";
     s << "typedef u32 v4 __attribute__((ext_vector_type(4)));\n";
@@ -1537,8 +1385,7 @@ std::string jit_index_source(const std::vector<ipcr_index_shape> &shapes, const 
     s << "#define KMHI " << KMHI << "u // k-mer bits an entry keeps in y\n";
     s << "#define NBAS " << NBAS << "u // bases (and invalid flags) an entry keeps\n";
     s << "#define EMODE " << mode << " // entry layout: 0 = lane, row above the k-mer in y; 1 = row in y, lane above the flags in z; 2 = both in w\n";
-    s << "#define PAIRED " << (paired ? "true" : "false") << " // a shape's table: 2^12 words, low half = the keys of the older step of a pair, high half = of the newer\n";
-    s << "#define PFX_WORDS " << (paired ? "(T64N / 4u)" : "(T64N / 2u)") << " // uint16 rank prefixes, one per 64 keys\n";
+    s << "#define PFX_WORDS (T64N / 2u) // uint16 rank prefixes, one per 64 keys\n";
     s << "__device__ const unsigned char __attribute__((aligned(16))) BITTAB[32] = {";
     for (int b = 0; b < 32; ++b) s << (b ? ", " : "") << tab[(size_t)b];
     s << "}; // payload bit -> shape | steps back << 4\n";
@@ -1683,76 +1530,48 @@ __device__ __forceinline__ u32 check_entry(u32 idx, u64 km, u32 bad, int erow, u
          "  const u32 offA = ((rowA >> 2) * 3u + (jh & 1u)) * 256u + (rowA & 3u);\n"
          "  const u32 offB = ((rowB >> 2) * 3u + (jh & 1u)) * 256u + (rowB & 3u);\n"
          "  const u32 offI = ((rowI >> 2) * 3u + 2u) * 256u + (rowI & 3u);\n";
-    const bool dynamic = env_int("IPCR_INDEX_DYNAMIC", 1, 0, 1) != 0;
-    // Which counter?  A 128-byte line of the tiles holds four rows of EIGHT columns, a unit reads two of them: four
-    // consecutive units share every line they load.  With one counter for the chip those four go to whichever waves ask
-    // next -- usually on four different XCDs, each with an L2 of its own, and the line is fetched four times (PMC: 1.7-3.4 x
-    // the algorithmic bytes).  So the groups of four units are dealt to the XCDs in turn, one counter per XCD (work[8 +
-    // 32 x]), and a wave asks the counter of the XCD it runs on (HW_REG_XCC_ID: speed only -- every unit is taken exactly
-    // once whatever the placement); a wave whose counter has run out moves on to the next one, so the sweep still ends
-    // with every wave busy.  IPCR_INDEX_XCD=0: the one counter.
-    const bool per_xcd = dynamic && env_int("IPCR_INDEX_XCD", 1, 0, 1) != 0;
-    // The next unit is taken, and its first nine loads issued, under the walk of the current unit's last chunk
-    // (IPCR_INDEX_AHEAD=0: at the unit's start, where the wave waits for the counter and then for the loads).
-    const bool ahead = per_xcd && env_int("IPCR_INDEX_AHEAD", 1, 0, 1) != 0;
-    if (per_xcd) {
-        s << "  u32 xq = (u32)__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7u, xtries = 0u; // HW_REG_XCC_ID, bits 3:0\n"
-             "  auto take_unit = [&]() __attribute__((always_inline)) { // -> a unit of [0, ncolpairs), or something beyond: no unit is left\n"
-             "    u64 unit;\n"
-             "    for (;;) {\n"
-             "      u32 take = 0u;\n"
-             "      if (lane == 0u) take = atomicAdd(work + 8u + 32u * xq, 1u);\n"
-             "      take = (u32)__builtin_amdgcn_readfirstlane((int)take);\n"
-             "      unit = ((u64)(take >> 2) * 8u + xq) * 4u + (take & 3u); // ascending in take: a counter that has run out stays so\n"
-             "      if (unit < ncolpairs || ++xtries == 8u) break;\n"
-             "      xq = (xq + 1u) & 7u;\n"
-             "    }\n"
-             "    return unit;\n"
-             "  };\n";
-        if (ahead)
-            s << "  // a unit's first words as loaded: its last chunk (the history of lane + 1), its first chunk, bit 31 of the column before\n"
-                 "  u32 nSA = 0u, nSB = 0u, nSI = 0u, nA = 0u, nB = 0u, nI = 0u, nH0 = 0u, nH1 = 0u;\n"
-                 "  auto issue_unit = [&](u64 unit) __attribute__((always_inline)) {\n"
-                 "    const u64 ncp = cp0 + unit, ncol = ncp * 2u + (lane >> 5);\n"
-                 "    const u32* const nbase = planes + (((ncol >> 6) * 6144u + (ncol & 63u)) << 2);\n"
-                 "    nSA = nbase[offA + 18432u]; nSB = nbase[offB + 18432u]; nSI = nbase[offI + 18432u];\n"
-                 "    nA = nbase[offA]; nB = nbase[offB]; nI = nbase[offI];\n"
-                 "    if (ncp != 0ull) {\n"
-                 "      const u64 pcol = ncp * 2u - 1u;\n"
-                 "      const u32* const pbase = planes + (((pcol >> 6) * 6144u + (pcol & 63u)) << 2);\n"
-                 "      nH0 = pbase[(lane < 32u ? offA : offB) + 18432u]; nH1 = pbase[offI + 18432u];\n"
-                 "    }\n"
-                 "  };\n"
-                 "  u64 nunit = take_unit();\n"
-                 "  if (nunit < ncolpairs) issue_unit(nunit);\n"
-                 "  for (;;) { // one unit = one column pair = 64 strands\n"
-                 "    if (nunit >= ncolpairs) break;\n"
-                 "    const u64 cp = cp0 + nunit;\n";
-        else
-            s << "  for (;;) { // one unit = one column pair = 64 strands\n"
-                 "    const u64 unit = take_unit();\n"
-                 "    if (unit >= ncolpairs) break;\n"
-                 "    const u64 cp = cp0 + unit;\n";
-    }
-    else if (dynamic)
-        // Units are handed out by a counter (work[0]): the waves of a persistent grid do not all run at the same pace (with a
-        // fixed share each, the 16 waves of a CU ended between 67 % and 100 % of the sweep: 7.29 ms per 3 Gb, 6.30 ms with the
-        // counter).  The last wave to leave zeroes the counters again (work[32] counts the leavers): nothing to clear between launches.
-        s << "  for (;;) { // one unit = one column pair = 64 strands\n"
-             "    u32 take = 0u;\n"
-             "    if (lane == 0u) take = atomicAdd(work, 1u);\n"
-             "    if ((u64)(u32)__builtin_amdgcn_readfirstlane((int)take) >= ncolpairs) break;\n"
-             "    const u64 cp = cp0 + (u64)(u32)__builtin_amdgcn_readfirstlane((int)take);\n";
-    else
-        s << "  for (u64 cp = cp0 + wave0; cp < cp0 + ncolpairs; cp += nwaves) { // one unit = one column pair = 64 strands\n";
+    // Units are handed out by counters: the waves of a persistent grid do not all run at the same pace.  A 128-byte line of
+    // the tiles holds four rows of EIGHT columns, a unit reads two of them: four consecutive units share every line they
+    // load.  So the groups of four units are dealt to the XCDs in turn, one counter per XCD (work[8 + 32 x]), and a wave
+    // asks the counter of the XCD it runs on (HW_REG_XCC_ID: speed only -- every unit is taken exactly once whatever the
+    // placement); a wave whose counter has run out moves on to the next one, so the sweep still ends with every wave busy.
+    // The next unit is taken, and its first nine loads issued, under the walk of the current unit's last chunk.  The last
+    // wave to leave zeroes the counters again (work[32] counts the leavers): nothing to clear between launches.
+    s << "  u32 xq = (u32)__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7u, xtries = 0u; // HW_REG_XCC_ID, bits 3:0\n"
+         "  auto take_unit = [&]() __attribute__((always_inline)) { // -> a unit of [0, ncolpairs), or something beyond: no unit is left\n"
+         "    u64 unit;\n"
+         "    for (;;) {\n"
+         "      u32 take = 0u;\n"
+         "      if (lane == 0u) take = atomicAdd(work + 8u + 32u * xq, 1u);\n"
+         "      take = (u32)__builtin_amdgcn_readfirstlane((int)take);\n"
+         "      unit = ((u64)(take >> 2) * 8u + xq) * 4u + (take & 3u); // ascending in take: a counter that has run out stays so\n"
+         "      if (unit < ncolpairs || ++xtries == 8u) break;\n"
+         "      xq = (xq + 1u) & 7u;\n"
+         "    }\n"
+         "    return unit;\n"
+         "  };\n"
+         "  // a unit's first words as loaded: its last chunk (the history of lane + 1), its first chunk, bit 31 of the column before\n"
+         "  u32 nSA = 0u, nSB = 0u, nSI = 0u, nA = 0u, nB = 0u, nI = 0u, nH0 = 0u, nH1 = 0u;\n"
+         "  auto issue_unit = [&](u64 unit) __attribute__((always_inline)) {\n"
+         "    const u64 ncp = cp0 + unit, ncol = ncp * 2u + (lane >> 5);\n"
+         "    const u32* const nbase = planes + (((ncol >> 6) * 6144u + (ncol & 63u)) << 2);\n"
+         "    nSA = nbase[offA + 18432u]; nSB = nbase[offB + 18432u]; nSI = nbase[offI + 18432u];\n"
+         "    nA = nbase[offA]; nB = nbase[offB]; nI = nbase[offI];\n"
+         "    if (ncp != 0ull) {\n"
+         "      const u64 pcol = ncp * 2u - 1u;\n"
+         "      const u32* const pbase = planes + (((pcol >> 6) * 6144u + (pcol & 63u)) << 2);\n"
+         "      nH0 = pbase[(lane < 32u ? offA : offB) + 18432u]; nH1 = pbase[offI + 18432u];\n"
+         "    }\n"
+         "  };\n"
+         "  u64 nunit = take_unit();\n"
+         "  if (nunit < ncolpairs) issue_unit(nunit);\n"
+         "  for (;;) { // one unit = one column pair = 64 strands\n"
+         "    if (nunit >= ncolpairs) break;\n"
+         "    const u64 cp = cp0 + nunit;\n";
     // The drain.  The queue is a STACK: a round takes the newest 64 entries, and what it hands back (an entry's further key
     // hits, a key's further patterns) goes into the slots it has just read, on top of the older entries -- so the next round
     // is again 64 entries wide.  A drain in the middle of a unit stops below 64 entries (they wait for company); only the
-    // unit's last drain runs rounds that are not full.  (Until late in round 3 the queue was emptied front to back at every
-    // drain and the handed-back entries -- a fifth of a pass -- in passes of their own, at a fifth of the lanes and less:
-    // 0.23 rounds per base step where the hits fill 0.13.  IPCR_INDEX_STACK_DRAIN=0 is that form.)
-    const bool stack_drain = env_int("IPCR_INDEX_STACK_DRAIN", 1, 0, 1) != 0;
-    if (stack_drain) {
+    // unit's last drain runs rounds that are not full.
     s << "    auto flush = [&](bool all) __attribute__((always_inline)) {\n"
          "      u32 n = qn;\n"
          "      const u64 unit_base = cp * 8192u; // first position of this unit\n"
@@ -1782,21 +1601,9 @@ __device__ __forceinline__ u32 check_entry(u32 idx, u64 km, u32 bad, int erow, u
          "          const v4 sc = *reinterpret_cast<const v4*>(lds + SHAPE_WORD0 + 4u * sidx); // {shifts, masks, first bitmap word, first entry}\n"
          "          const u32 key = ((u32)(skm >> (sc.x & 63u)) & (sc.y & 0xFFFFu)) | (((u32)(skm >> ((sc.x >> 8) & 63u)) & (sc.y >> 16)) << ((sc.x >> 16) & 31u));\n"
          "          // the key is in the panel; its rank among the shape's keys is the index of its entry\n"
-         "          if (PAIRED) { // keys are ranked as the OLDER step of a pair files them: word = the key's low 4 + 8 bits, bit = its high 2 + 2\n"
-         "            const u32 dw = sc.z * 2u + (((key >> 2) & 0xFF0u) | (key & 15u)), bo = ((key >> 14) << 2) | ((key >> 4) & 3u);\n"
-         "            const v4 g4 = *reinterpret_cast<const v4*>(lds + (dw & ~3u)); // the 64 keys (four words' low halves) one prefix covers\n"
-         "            const u32 pos = dw & 3u;\n"
-         "            const u32 own = pos == 0u ? g4.x : (pos == 1u ? g4.y : (pos == 2u ? g4.z : g4.w));\n"
-         "            u32 r = (u32)__builtin_popcount(own & ((1u << bo) - 1u));\n"
-         "            if (pos > 0u) r += (u32)__builtin_popcount(g4.x & 0xFFFFu);\n"
-         "            if (pos > 1u) r += (u32)__builtin_popcount(g4.y & 0xFFFFu);\n"
-         "            if (pos > 2u) r += (u32)__builtin_popcount(g4.z & 0xFFFFu);\n"
-         "            idx = sc.w + (u32)prefix[dw >> 2] + r;\n"
-         "          } else {\n"
-         "            const u32 wi = sc.z + (key >> 6); // the shape's bitmap word with this key\n"
-         "            const u64 w = T64[wi];\n"
-         "            idx = sc.w + (u32)prefix[wi] + (u32)__popcll((w << (63u - (key & 63u))) << 1);\n"
-         "          }\n"
+         "          const u32 wi = sc.z + (key >> 6); // the shape's bitmap word with this key\n"
+         "          const u64 w = T64[wi];\n"
+         "          idx = sc.w + (u32)prefix[wi] + (u32)__popcll((w << (63u - (key & 63u))) << 1);\n"
          "        }\n"
          "        u32 next = 0xFFFFFFFFu;\n"
          "        if (idx != 0xFFFFFFFFu) {\n"
@@ -1822,84 +1629,10 @@ __device__ __forceinline__ u32 check_entry(u32 idx, u64 km, u32 bad, int erow, u
          "      }\n"
          "      qn = n;\n"
          "    };\n";
-    } else
-    s << "    auto flush = [&](bool) __attribute__((always_inline)) {\n"
-         "      u32 n = qn;\n"
-         "      const u64 unit_base = cp * 8192u; // first position of this unit\n"
-         "      const u32 shard = (u32)cp & 255u;\n"
-         "      while (n != 0u) {\n"
-         "        u32 nc = 0u; // entries handed back so far: slots [0, nc), always behind the round being read\n"
-         "        auto hand_back = [&](bool mine, v4 e, u32 w) __attribute__((always_inline)) {\n"
-         "          const u64 rb = __ballot(mine);\n"
-         "          if (rb != 0ull) {\n"
-         "            if (mine) {\n"
-         "              const u32 slot = nc + __builtin_amdgcn_mbcnt_hi((u32)(rb >> 32), __builtin_amdgcn_mbcnt_lo((u32)rb, 0u));\n"
-         "              e.w = w;\n"
-         "              *reinterpret_cast<v4*>(wq + slot * 4u) = e;\n"
-         "            }\n"
-         "            nc += (u32)__popcll(rb);\n"
-         "          }\n"
-         "        };\n"
-         "        for (u32 qb = 0; qb < n; qb += 64u) {\n"
-         "          const u32 i = qb + lane;\n"
-         "          v4 e = *reinterpret_cast<const v4*>(wq + i * 4u); // (a slot behind the last entry is still inside the queue: n <= QCAP, a multiple of 64)\n"
-         "          if (i >= n) e.w = 0u; // nothing pending, no chain: the lane idles through the round\n"
-         "          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, \"wavefront\"); // every lane has read its slot: slots up to qb + 63 may be rewritten\n"
-         "          u32 pend = 0u, idx = 0xFFFFFFFFu, back = 0u, keep = 0u; // keep: what of w a handed-back entry keeps (layout C: lane and row)\n"
-         "          u32 elane, erow0;\n"
-         "          u64 hkm; u32 hbad;\n"
-         "          if (EMODE == 0) { hkm = ((u64)(KMHI ? (e.y & ((1u << KMHI) - 1u)) : 0u) << 32) | e.x; hbad = e.z; elane = (e.y >> KMHI) & 63u; erow0 = (e.y >> (KMHI + 6u)) & ((1u << ROWB) - 1u); }\n"
-         "          else if (EMODE == 1) { hkm = ((u64)(KMHI ? (e.y & ((1u << KMHI) - 1u)) : 0u) << 32) | e.x; hbad = e.z & ((1u << NBAS) - 1u); elane = e.z >> NBAS; erow0 = (e.y >> KMHI) & ((1u << ROWB) - 1u); }\n"
-         "          else { hkm = ((u64)e.y << 32) | e.x; hbad = e.z; elane = (e.w >> 15) & 63u; erow0 = (e.w >> 21) & ((1u << ROWB) - 1u); keep = e.w & 0x7FFF8000u; }\n"
-         "          const u32 pay = EMODE == 2 ? (e.w & 0x7FFFu) : (e.w & 0x7FFFFFFFu);\n"
-         "          if (e.w & 0x80000000u) { idx = pay >> 2; back = pay & 3u; }\n"
-         "          else pend = pay;\n"
-         "          const u32 rest = pend & (pend - 1u);\n"
-         "          hand_back(rest != 0u, e, keep | rest); // (k-mer, flags and row as filed)\n"
-         "          if (pend != 0u) {\n"
-         "            const u32 t = reinterpret_cast<const unsigned char*>(lds + TAB_WORD0)[__builtin_ctz(pend)];\n"
-         "            const u32 sidx = t & 15u;\n"
-         "            back = t >> 4;\n"
-         "            const u64 skm = hkm >> (2u * back); // a hit of an earlier step of the entry: its own k-mer\n"
-         "            const v4 sc = *reinterpret_cast<const v4*>(lds + SHAPE_WORD0 + 4u * sidx); // {shifts, masks, first bitmap word, first entry}\n"
-         "            const u32 key = ((u32)(skm >> (sc.x & 63u)) & (sc.y & 0xFFFFu)) | (((u32)(skm >> ((sc.x >> 8) & 63u)) & (sc.y >> 16)) << ((sc.x >> 16) & 31u));\n"
-         "            // the key is in the panel; its rank among the shape's keys is the index of its entry\n"
-         "            if (PAIRED) { // keys are ranked as the OLDER step of a pair files them: word = the key's low 4 + 8 bits, bit = its high 2 + 2\n"
-         "              const u32 dw = sc.z * 2u + (((key >> 2) & 0xFF0u) | (key & 15u)), bo = ((key >> 14) << 2) | ((key >> 4) & 3u);\n"
-         "              const v4 g4 = *reinterpret_cast<const v4*>(lds + (dw & ~3u)); // the 64 keys (four words' low halves) one prefix covers\n"
-         "              const u32 pos = dw & 3u;\n"
-         "              const u32 own = pos == 0u ? g4.x : (pos == 1u ? g4.y : (pos == 2u ? g4.z : g4.w));\n"
-         "              u32 r = (u32)__builtin_popcount(own & ((1u << bo) - 1u));\n"
-         "              if (pos > 0u) r += (u32)__builtin_popcount(g4.x & 0xFFFFu);\n"
-         "              if (pos > 1u) r += (u32)__builtin_popcount(g4.y & 0xFFFFu);\n"
-         "              if (pos > 2u) r += (u32)__builtin_popcount(g4.z & 0xFFFFu);\n"
-         "              idx = sc.w + (u32)prefix[dw >> 2] + r;\n"
-         "            } else {\n"
-         "              const u32 wi = sc.z + (key >> 6); // the shape's bitmap word with this key\n"
-         "              const u64 w = T64[wi];\n"
-         "              idx = sc.w + (u32)prefix[wi] + (u32)__popcll((w << (63u - (key & 63u))) << 1);\n"
-         "            }\n"
-         "          }\n"
-         "          u32 next = 0xFFFFFFFFu;\n"
-         "          if (idx != 0xFFFFFFFFu) {\n"
-         "            const u64 skm = hkm >> (2u * back);\n"
-         "            const u32 sbad = hbad >> back;\n"
-         "            const u32 strand_off = elane << 7;\n"
-         "            const int erow = (int)erow0 - (int)back;\n"
-         "            next = check_entry(idx, skm, sbad, erow, unit_base, strand_off, shard, table, max_mm, queue, qcap, qcount, fu, ncand);\n"
-         "            if (!CHAIN_CARRY || rest != 0u)\n"
-         "              while (next != 0xFFFFFFFFu) next = check_entry(next, skm, sbad, erow, unit_base, strand_off, shard, table, max_mm, queue, qcap, qcount, fu, ncand);\n"
-         "          }\n"
-         "          if (CHAIN_CARRY) hand_back(next != 0xFFFFFFFFu, e, keep | 0x80000000u | (next << 2) | back);\n"
-         "        }\n"
-         "        n = nc;\n"
-         "        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, \"wavefront\"); // the entries handed back are read by other lanes next\n"
-         "      }\n"
-         "      qn = 0;\n"
-         "      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, \"wavefront\"); // queue slots are rewritten by other lanes next\n"
-         "    };\n";
     // the unit's tiles: column 2 cp + (lane >> 5)
-    if (ahead)
+    // history: the strand before mine ended with its chunk 3 -- lane - 1's, which is transposed first (and kept: the walk
+    // comes back to it); lane 0's predecessor is strand 31 of the column before the unit's first: bit 31 of that column's
+    // words, gathered by a ballot over the lanes that load them (half 0: the rows of word A, half 1: those of word B)
     s << "    const u64 col = cp * 2u + (lane >> 5);\n"
          "    const u32* const base = planes + (((col >> 6) * 6144u + (col & 63u)) << 2);\n"
          "    // (the words were loaded under the unit before: issue_unit)\n"
@@ -1915,29 +1648,8 @@ __device__ __forceinline__ u32 check_entry(u32 idx, u64 km, u32 bad, int erow, u
          "      if (lane == 0u) { PA = hA; PB = hB; PI = hI; }\n"
          "    }\n"
          "    u32 A = tr32(nA, tc), B = tr32(nB, tc), I = tr32(nI, tc);\n";
-    else
-    s << "    const u64 col = cp * 2u + (lane >> 5);\n"
-         "    const u32* const base = planes + (((col >> 6) * 6144u + (col & 63u)) << 2);\n"
-         "    // history: the strand before mine ended with its chunk 3 -- lane - 1's, which is loaded and transposed first (and kept: the\n"
-         "    // walk comes back to it); lane 0's predecessor is strand 31 of the column before the unit's first: bit 31 of that column's\n"
-         "    // words, gathered by a ballot over the lanes that load them (half 0: the rows of word A, half 1: those of word B)\n"
-         "    const u32 SA = tr32(base[offA + 18432u], tc), SB = tr32(base[offB + 18432u], tc), SI = tr32(base[offI + 18432u], tc);\n"
-         "    u32 PA = (u32)__shfl_up((int)SA, 1), PB = (u32)__shfl_up((int)SB, 1), PI = (u32)__shfl_up((int)SI, 1);\n"
-         "    {\n"
-         "      u32 hA = 0u, hB = 0u, hI = 0xFFFFFFFFu; // the very first strand: nothing but invalid bases in front of it\n"
-         "      if (cp != 0ull) {\n"
-         "        const u64 pcol = cp * 2u - 1u;\n"
-         "        const u32* const pbase = planes + (((pcol >> 6) * 6144u + (pcol & 63u)) << 2);\n"
-         "        const u64 bk = __ballot((pbase[(lane < 32u ? offA : offB) + 18432u] >> 31) != 0u);\n"
-         "        const u64 bi = __ballot((pbase[offI + 18432u] >> 31) != 0u);\n"
-         "        hA = (u32)bk; hB = (u32)(bk >> 32); hI = (u32)bi;\n"
-         "      }\n"
-         "      if (lane == 0u) { PA = hA; PB = hB; PI = hI; }\n"
-         "    }\n"
-         "    u32 A = tr32(base[offA], tc), B = tr32(base[offB], tc), I = tr32(base[offI], tc);\n";
     s << "    u32 rA = 0u, rB = 0u, rI = 0u; // the next chunk's words as loaded\n"
          "    u32 acc = 0u; // the masks of the steps since the last queue entry\n";
-    for (unsigned j = 0; j < NCH && paired; ++j) s << "    u32 acc" << j << " = 0u;\n";
     if (mode == 0) s << "    const u32 lane_y = lane << KMHI; // this lane's part of an entry's y\n";
     if (mode == 1) s << "    const u32 lane_z = lane << NBAS;\n";
     if (mode == 2) s << "    const u32 lane_w = lane << 15;\n";
@@ -1945,60 +1657,10 @@ __device__ __forceinline__ u32 check_entry(u32 idx, u64 km, u32 bad, int erow, u
          "    bool done = false;\n"
          "    while (!done) {\n";
     // A queue entry's SPE steps are ONE block of code (a drain resumes behind an entry).  Their lookups are independent of
-    // one another -- every key field is a constant slice of the same three registers.  IPCR_INDEX_PHASED=1 issues all the
-    // block's LDS reads before any test (24 in flight for C4): measured 3 % SLOWER than letting every step wait for its
-    // own six (the LDS is the busy unit, 81 % of the sweep: bursts only queue up behind one another).
-    const bool phased = env_int("IPCR_INDEX_PHASED", 0, 0, 1) != 0;
+    // one another -- every key field is a constant slice of the same three registers: the block's addresses and LDS reads
+    // are emitted first (pa), its tests behind them (pb).
     for (unsigned k0 = 0; k0 < U; k0 += SPE) {
         std::ostringstream pa, pb; // phase A (addresses, reads), phase B (tests)
-        if (paired) {
-            unsigned cc = 0; // tests made so far in this block
-            auto test = [&](const std::string &word, const std::string &idx) {
-                const std::string a = "acc" + std::to_string(cc % NCH);
-                if (use_add) pb << "        " << a << " = ANDOR(" << word << " >> " << idx << ", 1u, " << a << " + " << a << ");\n";
-                else pb << "        " << a << " = __builtin_amdgcn_alignbit(" << word << " >> " << idx << ", " << a << ", 1u);\n";
-                ++cc;
-            };
-            for (unsigned kn = k0 + 1u; kn < k0 + SPE; kn += 2u) { // the pair (kn - 1, kn), every field taken in the frame of step kn
-                const unsigned half = kn / 16u, tq = kn % 16u, P0 = 2u * (15u - tq);
-                const char *W[3] = {half ? "B" : "A", half ? "A" : "PB", half ? "PB" : "PA"};
-                auto shifted = [&](unsigned f, unsigned width) { // (km >> f), valid in its low `width` bits at least; km = {W2, W1, W0} >> P0
-                    const unsigned P = P0 + f, q = P / 32u, r = P % 32u;
-                    if (q > 2u) return std::string("0u");
-                    if (r == 0u) return std::string(W[q]);
-                    if (r + width <= 32u || q == 2u) return "(" + std::string(W[q]) + " >> " + std::to_string(r) + "u)";
-                    return "__builtin_amdgcn_alignbit(" + std::string(W[q + 1]) + ", " + W[q] + ", " + std::to_string(r) + "u)";
-                };
-                auto width_of = [](unsigned mask) { unsigned w = 0; while (mask >> w) ++w; return w; };
-                auto field = [&](unsigned f, unsigned mask) { return "(" + shifted(f, width_of(mask)) + " & " + std::to_string(mask) + "u)"; };
-                const std::string K = std::to_string(kn);
-                pa << "        // steps " << kn - 1u << ", " << kn << "\n";
-                for (size_t gi = 0; gi < groups.size(); ++gi) {
-                    const unsigned c = (unsigned)groups[gi].c_off; // the protected bases: 8 bits of the two steps together
-                    const std::string G = std::to_string(gi) + "_" + K;
-                    pa << "        const u32 cp" << G << " = " << field(c, 0x3Cu) << ", un" << G << " = ANDOR(" << shifted(c, 2u) << ", 3u, 16u), uo" << G << " = " << field(c + 6u, 3u) << ";\n";
-                    for (int si : groups[gi].sh) {
-                        const unsigned b = (unsigned)shapes[(size_t)si].blk_shift; // the block: 12 bits of the two steps together
-                        const std::string S = std::to_string(si) + "_" + K;
-                        const std::string addr = b >= 4u ? "ANDOR(" + shifted(b - 4u, 14u) + ", 16320u, cp" + G + ")" : "((" + field(b + 2u, 255u) + " << 6) | cp" + G + ")";
-                        const std::string inew = b >= 2u ? "ANDOR(" + shifted(b - 2u, 4u) + ", 12u, un" + G + ")" : "((" + field(b, 3u) + " << 2) | un" + G + ")";
-                        const std::string iold = "ANDOR(" + shifted(b + 8u, 4u) + ", 12u, uo" + G + ")";
-                        pa << "        const u32 w" << S << " = *reinterpret_cast<const u32*>(ldsb + " << off64[(size_t)si] * 8u << "u + " << addr << ");\n";
-                        test("w" + S, iold);
-                        test("w" + S, inew);
-                    }
-                }
-            }
-            if (use_add) {
-                pb << "        acc = (acc0 & " << ((1u << NPC) - 1u) << "u)";
-                for (unsigned j = 1; j < NCH; ++j) pb << " | ((acc" << j << " & " << ((1u << NPC) - 1u) << "u) << " << j * NPC << "u)";
-                pb << ";\n";
-            } else {
-                pb << "        acc = (acc0 >> " << 32u - NPC << "u)";
-                for (unsigned j = 1; j < NCH; ++j) pb << " | ((acc" << j << " >> " << 32u - NPC << "u) << " << j * NPC << "u)";
-                pb << ";\n";
-            }
-        } else
         for (unsigned k = k0; k < k0 + SPE; ++k) {
             const unsigned half = k / 16u, tq = k % 16u, P0 = 2u * (15u - tq);
             const char *W[3] = {half ? "B" : "A", half ? "A" : "PB", half ? "PB" : "PA"};
@@ -2073,11 +1735,9 @@ __device__ __forceinline__ u32 check_entry(u32 idx, u64 km, u32 bad, int erow, u
         s << "      if (u == " << k0 << "u) {\n";
         if (k0 == 0) {
             s << "        if (it < 2u) { rA = base[offA + (it + 1u) * 6144u]; rB = base[offB + (it + 1u) * 6144u]; rI = base[offI + (it + 1u) * 6144u]; }\n";
-            if (ahead)
-                s << "        if (it == 3u) { nunit = take_unit(); if (nunit < ncolpairs) issue_unit(nunit); } // the next unit, under this chunk's walk\n";
+            s << "        if (it == 3u) { nunit = take_unit(); if (nunit < ncolpairs) issue_unit(nunit); } // the next unit, under this chunk's walk\n";
         }
         s << pa.str();
-        if (phased) s << "        __builtin_amdgcn_sched_barrier(0);\n";
         s << pb.str();
         {
             const std::string kmlo = P0 ? "__builtin_amdgcn_alignbit(" + std::string(W[1]) + ", " + W[0] + ", " + std::to_string(P0) + "u)" : std::string(W[0]);
@@ -2114,30 +1774,29 @@ __device__ __forceinline__ u32 check_entry(u32 idx, u64 km, u32 bad, int erow, u
          "      if (full || done) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, \"wavefront\"); flush(done); }\n"
          "    }\n";
     s << "  }\n"; // (rows are relative to the unit: the queue is always empty when a unit ends)
-    if (dynamic)
-        s << "  if (hits) { // fused: the candidate statistics (one atomic per workgroup), and every record of this wave on its way before it leaves\n"
-             "    u32 cs = ncand;\n"
-             "    for (int off = 32; off > 0; off >>= 1) cs += __shfl_down(cs, off);\n"
-             "    if (lane == 0u && cs != 0u) atomicAdd(&wg_cand, cs);\n"
-             "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
-             "    __syncthreads();\n"
-             "    if (threadIdx.x == 0u && wg_cand != 0u) { atomicAdd(counts + 2, (u64)wg_cand); asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\"); }\n"
-             "  }\n"
-             "  u32 last = 0u;\n"
-             "  if (lane == 0u) {\n"
-             "    const u32 left = atomicAdd(work + 32u, 1u);\n"
-             "    if ((u64)left + 1ull == nwaves) {\n"
-             "      last = 1u;\n"
-             "      __hip_atomic_store(work, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(work + 32u, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-          << (per_xcd ? "      for (u32 x = 0; x < 8u; ++x) __hip_atomic_store(work + 8u + 32u * x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n" : "") <<
-             "    }\n"
-             "  }\n"
-             "  if (__builtin_amdgcn_readfirstlane((int)last) != 0 && pub) { // every other wave of the scan has left: hand the counters to the host\n"
-             "    __threadfence();\n"
-             "    if (lane < 4u) pub[lane] = __hip_atomic_load(counts + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-             "    __threadfence_system();\n"
-             "    if (lane == 0u) __hip_atomic_store(pub_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);\n"
-             "  }\n";
+    s << "  if (hits) { // fused: the candidate statistics (one atomic per workgroup), and every record of this wave on its way before it leaves\n"
+         "    u32 cs = ncand;\n"
+         "    for (int off = 32; off > 0; off >>= 1) cs += __shfl_down(cs, off);\n"
+         "    if (lane == 0u && cs != 0u) atomicAdd(&wg_cand, cs);\n"
+         "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+         "    __syncthreads();\n"
+         "    if (threadIdx.x == 0u && wg_cand != 0u) { atomicAdd(counts + 2, (u64)wg_cand); asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\"); }\n"
+         "  }\n"
+         "  u32 last = 0u;\n"
+         "  if (lane == 0u) {\n"
+         "    const u32 left = atomicAdd(work + 32u, 1u);\n"
+         "    if ((u64)left + 1ull == nwaves) {\n"
+         "      last = 1u;\n"
+         "      __hip_atomic_store(work, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(work + 32u, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+         "      for (u32 x = 0; x < 8u; ++x) __hip_atomic_store(work + 8u + 32u * x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+         "    }\n"
+         "  }\n"
+         "  if (__builtin_amdgcn_readfirstlane((int)last) != 0 && pub) { // every other wave of the scan has left: hand the counters to the host\n"
+         "    __threadfence();\n"
+         "    if (lane < 4u) pub[lane] = __hip_atomic_load(counts + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+         "    __threadfence_system();\n"
+         "    if (lane == 0u) __hip_atomic_store(pub_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);\n"
+         "  }\n";
     s << "  if (stamps && lane == 0u) stamps[wave0 * 2u + 1u] = __builtin_amdgcn_s_memrealtime();\n";
     s << "}\n";
     return s.str();
@@ -2167,7 +1826,7 @@ JitFilter *jit_build_index(const std::vector<ipcr_index_shape> &shapes, const In
     return f; // the kernel's LDS (image + hit queues, up to 160 KiB) is static: nothing to request at launch
 }
 
-bool jit_index_fusable() { return env_int("IPCR_INDEX_DYNAMIC", 1, 0, 1) != 0 && env_int("IPCR_INDEX_FUSED", 1, 0, 1) != 0; }
+bool jit_index_fusable() { return env_int("IPCR_INDEX_FUSED", 1, 0, 1) != 0; }
 
 hipError_t jit_launch_index(JitFilter *f, hipStream_t st, const uint32_t *planes, uint64_t block0, uint64_t nblocks, uint32_t /*nshapes*/,
                             const uint32_t *lds_image, const void *table, uint32_t max_mm, void *queue,

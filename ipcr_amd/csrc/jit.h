@@ -72,9 +72,6 @@ struct IndexGeom {
     uint32_t table_entries = 0; // entries of the panel's table: chained patterns of a key go back into the queue when an entry index fits the bits a queue entry has for it
 };
 std::string jit_index_source(const std::vector<ipcr_index_shape> &shapes, const IndexGeom &geom);
-// can a panel of n_shapes shapes (all "3 protected bases + 5 block bases") whose windows reach tail_rows bases back take
-// the two-steps-per-lookup tables?  (host.cpp: build_index asks before it lays the tables out; IPCR_INDEX_TWO_STEP=0: no)
-bool jit_index_pairable(size_t n_shapes, int tail_rows);
 // bytes of the LDS image of a set of shapes (tables + rank prefixes + constants)
 unsigned jit_index_image_bytes(const std::vector<ipcr_index_shape> &shapes);
 JitFilter *jit_build_index(const std::vector<ipcr_index_shape> &shapes, const IndexGeom &geom, std::string &err);
@@ -82,10 +79,11 @@ hipError_t jit_launch_index(JitFilter *f, hipStream_t st, const uint32_t *planes
                             const uint32_t *lds_image, const void *table, uint32_t max_mm, void *queue,
                             uint64_t qcap, unsigned long long *qcount, uint32_t *work, hipEvent_t start, hipEvent_t stop,
                             const JitVerify *fused = nullptr);
-// work: two zeroed counters 128 B apart (unit counter, leavers); the kernel leaves them zeroed again
+// work: zeroed counters 128 B apart (a unit counter per XCD at word 8 + 32 x, the leavers at word 32); the kernel leaves them
+// zeroed again
 // fused: the index kernel writes the hit records itself and its last wave hands the counters to the host (as the specialised
-// filter does: JitVerify; tickets / withhold unused) -- for panels whose every pattern the index serves (no leftovers) and
-// when jit_index_fusable() (the dynamic unit hand-out is on: the last wave to leave is what publishes)
+// filter does: JitVerify; tickets / withhold unused; the last wave to leave is what publishes) -- for panels whose every
+// pattern the index serves (no leftovers) and when jit_index_fusable() (IPCR_INDEX_FUSED is not 0)
 bool jit_index_fusable();
 void jit_destroy(JitFilter *f);
 

@@ -202,15 +202,14 @@ def test_random_differential(hip, spec, seed):
         check(hip, cfg, "".join(seq).encode(), pairs, specialize=spec)
 
 
-@pytest.mark.parametrize("roll", [0, 1, 2])
+@pytest.mark.parametrize("roll", [0, 1])
 def test_windows_across_strand_and_block_ends(hip, monkeypatch, roll):
     """sites planted so that their windows start in the last rows of a strand (p % 128 in 100..127: the wrap rows, read
     from the stashed head quads of the neighbour column) and across block ends (p % 8192 near 8191: lane 63's neighbour
     is column 0 of the next block), forward and reverse, 0-2 mismatches, with junk bytes; the specialised filter in
-    its default form (iteration 0, main loop, static epilogue), as one rolled loop over all quads (IPCR_JIT_ROLL=1) and
-    with a 24-slot window and one rare-branch test per quad (IPCR_JIT_MERGE=1; jit.cpp); vs the oracle"""
-    monkeypatch.setenv("IPCR_JIT_ROLL", str(roll & 1))   # read when the kernel's source is generated (first scan)
-    monkeypatch.setenv("IPCR_JIT_MERGE", str(roll >> 1))  # 2: a 24-slot register window, one rare-branch test per row quad
+    its default form (iteration 0, main loop, static epilogue) and as one rolled loop over all quads (IPCR_JIT_ROLL=1;
+    jit.cpp); vs the oracle"""
+    monkeypatch.setenv("IPCR_JIT_ROLL", str(roll))   # read when the kernel's source is generated (first scan)
     rng = random.Random(4242 + roll)
     E, P = hip.engine, hip.primer.Pair
     for n, k, tw in ((34000, 2, 5), (18000, 3, 3), (34000, 0, 0)):
@@ -992,14 +991,12 @@ def test_index_filter_random(hip, force_index, monkeypatch, seed):
     assert 3 in kinds
 
 
-@pytest.mark.parametrize("half_bases,two_step", [(0, 0), (1, 0), (0, 1)])
-def test_config_c4_large_panel_index(hip, monkeypatch, half_bases, two_step):
-    """256 TSV rows -> 768 pairs / 1024 distinct patterns: seed-index filter, vs the oracle; with 16-bit keys, with the
-    17-bit keys (a block takes one bit of a spare sixth base: host.cpp build_index, the default), and with the tables
-    that serve two base steps per lookup (jit.cpp, IPCR_INDEX_TWO_STEP: measured slower, kept as a knob)"""
+@pytest.mark.parametrize("half_bases", [0, 1])
+def test_config_c4_large_panel_index(hip, monkeypatch, half_bases):
+    """256 TSV rows -> 768 pairs / 1024 distinct patterns: seed-index filter, vs the oracle; with 16-bit keys and with the
+    17-bit keys (a block takes one bit of a spare sixth base: host.cpp build_index, the default)"""
     from ipcr_amd import workloads
     monkeypatch.setenv("IPCR_INDEX_HALF_BASES", str(half_bases))
-    monkeypatch.setenv("IPCR_INDEX_TWO_STEP", str(two_step))
     rng = random.Random(26)
     pairs = workloads.c4_pairs(256)
     g, seqs = build_planted_genome(hip, rng, 3, 400_000, pairs[:256], 0x5eed1239)
@@ -1221,11 +1218,9 @@ def test_k4_medium_panel_is_specialised_in_groups(hip):
     g.close()
 
 
-@pytest.mark.parametrize("stack", [1, 0, 2])
-def test_index_drain_under_chains_and_crowded_rounds(hip, force_index, monkeypatch, stack):
-    """(stack = 1: the drain takes the newest 64 entries per round and leaves fewer than 64 for the next drain of the
-    unit, jit.cpp: stack_drain; 0: the front-to-back form it replaced, still behind IPCR_INDEX_STACK_DRAIN=0, with the
-    units taken at their start; 2: the stack drain with one unit counter for the chip, IPCR_INDEX_XCD=0)
+def test_index_drain_under_chains_and_crowded_rounds(hip, force_index):
+    """(the drain takes the newest 64 entries per round and leaves fewer than 64 for the next drain of the unit, jit.cpp:
+    the drain is a stack)
     worst case for the seed-index drain: three families of 16 primers that differ only in two bases of one block
     (every key of the other blocks is shared by the whole family: entry chains of 16; an exact site is filed under
     all three shapes, and with k = 2 every site matches all 16 members) on a sequence
@@ -1249,10 +1244,6 @@ def test_index_drain_under_chains_and_crowded_rounds(hip, force_index, monkeypat
     unit[100:120] = rc
     seq = ("".join(unit) * 600).encode()            # 76 800 bases: 600 strands, each with the same sites
     cfg = E.Config(MaxMM=2, TerminalWindow=3, MinLen=0, MaxLen=120, HitCap=0, SeedLen=12)
-    monkeypatch.setenv("IPCR_INDEX_STACK_DRAIN", str(min(stack, 1)))   # read when the kernel's source is generated (first scan)
-    if stack == 2:   # the unit hand-out it replaced too: one counter for the chip, a unit's loads at its start
-        monkeypatch.setenv("IPCR_INDEX_XCD", "0")
-    monkeypatch.setenv("IPCR_INDEX_AHEAD", "0" if stack == 0 else "1")   # (no effect without the per-XCD counters)
     eng = E.New(cfg)
     cp = eng.CompilePanel(pairs)
     sc = eng.NewSimulationScratch(cp)

@@ -584,11 +584,7 @@ def test_seed_index_source_compiles_for_gfx950(k, tw, lens, iupac, tmp_path):
     src = cp.filter_source(2)
     cp.close()
     assert "ipcr_index_filter" in src
-    if "two steps per lookup" in src:                          # 3 protected + 5 block bases throughout: one ds_read_b32 per shape and PAIR of steps
-        assert re.search(r"const u32 cp0_1 = \(.*& 60u\), un0_1 = ANDOR\(.*, 3u, 16u\), uo0_1 = ", src), \
-            "the protected bases two consecutive steps share must be taken once per pair and group"
-        assert len(re.findall(r"reinterpret_cast<const u32\*>\(ldsb \+", src)) == 16 * src.count("#define NS ") * int(re.search(r"#define NS (\d+)", src).group(1))
-    elif tw >= 3 and k >= 1 and "(entry layout C)" not in src:   # (primers beyond 26 nt: one bit per shape, see jit.cpp)
+    if tw >= 3 and k >= 1 and "(entry layout C)" not in src:   # (primers beyond 26 nt: one bit per shape, see jit.cpp)
         assert re.search(r"const u32 cb0_0 = \(.*& 7u\), cw0_0 = ", src), \
             "a panel with >= 3 protected bases must take its shapes' common six key bits once per step"
     path = tmp_path / "index.hip"
@@ -599,6 +595,33 @@ def test_seed_index_source_compiles_for_gfx950(k, tw, lens, iupac, tmp_path):
     vgpr = int(re.search(r"\.vgpr_count:\s+(\d+)", asm).group(1))
     spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", asm).group(1))
     assert lds <= 160 * 1024 and vgpr <= 128 and spill <= 16, (lds, vgpr, spill)
+
+
+def test_removed_generator_knobs_have_no_effect(monkeypatch):
+    """the kernel forms that only a non-default environment variable selected were removed from the generators: with every
+    such variable at its old non-default value, the specialised filter (C2: modes 0, 1 and their small-launch forms 4, 5)
+    and the seed-index filter (C4: modes 2, 3) are generated exactly as with the variables unset"""
+    from ipcr_amd.workloads import c2_pairs, c4_pairs
+    removed = {"IPCR_INDEX_TWO_STEP": "1", "IPCR_INDEX_ACC_CHAINS": "2", "IPCR_INDEX_ACC_ADD": "1", "IPCR_INDEX_STACK_DRAIN": "0",
+               "IPCR_INDEX_DYNAMIC": "0", "IPCR_INDEX_XCD": "0", "IPCR_INDEX_AHEAD": "0", "IPCR_INDEX_PHASED": "1",
+               "IPCR_JIT_MERGE": "1", "IPCR_JIT_ONE_PUSH": "0", "IPCR_JIT_NEIGHBOUR": "0"}
+    cases = [(engine.Config(MaxMM=2, TerminalWindow=5, MaxLen=2000, HitCap=10000, SeedLen=12), c2_pairs(), (0, 1, 4, 5)),
+             (engine.Config(MaxMM=2, TerminalWindow=3, MaxLen=2000, HitCap=10000, SeedLen=12), c4_pairs(64), (2, 3))]
+
+    def sources():
+        out = []
+        for cfg, pairs, modes in cases:   # a new panel each time: the seed index is built once per panel
+            cp = engine.New(cfg).CompilePanel(pairs)
+            out += [cp.filter_source(m) for m in modes]
+            cp.close()
+        return out
+    for name in removed:
+        monkeypatch.delenv(name, raising=False)
+    want = sources()
+    assert all(want) and "ipcr_index_filter" in want[-1]
+    for name, value in removed.items():
+        monkeypatch.setenv(name, value)
+    assert sources() == want
 
 
 PACK_CHECK = r'''

@@ -2,7 +2,7 @@
 # dev tool (GPU box): A/B runs of one bench workload under generator / runtime knobs -- one run per stdin line,
 #   "<workload> [VAR=value ...]"        workload: c2 | c2n | c3 | c4 | c5 | chunk (the native worker pool: args after "--")
 # e.g.
-#   printf "c3\nc3 IPCR_JIT_PEEL=0\nc4\nc4 IPCR_INDEX_XCD=0\nchunk GPU_MAX_HW_QUEUES=8 -- 125000000 4000000 8 16\n" | bash tools/knobs.sh
+#   printf "c3\nc3 IPCR_JIT_PEEL=0\nc4\nc4 IPCR_INDEX_PACKED=0\nchunk GPU_MAX_HW_QUEUES=8 -- 125000000 4000000 8 16\n" | bash tools/knobs.sh
 # Alternate the lines (A, B, A, B): consecutive runs on one box differ by a per cent or two, boxes of the pool by five.
 # Prints sweep ms, roofline fraction, ms per step and the product count (every pass of every run is checked by bench.py).
 cd ${GRAFT_REPO_ROOT:-.}
