@@ -4,7 +4,7 @@ Only what sits directly either side of the scan path ("nex
 FASTA -> resident tiles, the collector's total product order, and the text/TSV rows -- with the
 reference's flag names and defaults (internal/clibase/common.go:61-110) so outputs can be
 diffed against `ipcr`.  --products (JSONL `seq`) and --output fasta carry the amplicon bytes, read exactly from the
-resident genome (ipcr_genome_read_windows).  Thermo scoring, pretty blocks and JSON are out of scope; nested PCR
+resident genome (ipcr_genome_read_windows).  The data paths (resident, --chunk-size, streamed chunks) are `ipcr_amd.pipeline`.  Thermo scoring, pretty blocks and JSON are out of scope; nested PCR
 is `ipcr_amd.nested_cli`.
 
     python -m ipcr_amd.cli -f AGAGTTTGATCMTGGCTCAG -r TACGGYTACCTTGTTAYGACTT --mismatches 0 demo.fa
@@ -12,13 +12,10 @@ is `ipcr_amd.nested_cli`.
 from __future__ import annotations
 
 import argparse
-import ctypes as C
-import functools
-import os
 import sys
 from typing import List, Optional, Sequence
 
-from . import _lib, engine, primer
+from . import engine, pipeline, primer
 
 TSV_HEADER = ("source_file\tsequence_id\texperiment_id\tstart\tend\tlength\ttype\tfwd_mm\trev_mm"
               "\tfwd_mm_i\trev_mm_i")                                   # internal/output/common.go:5
@@ -192,44 +189,19 @@ def _text(b: bytes) -> str:
     return b.decode("latin-1")  # one character per byte: bytes >= 0x80 are kept as they were loaded
 
 
-def _record_seqs(path: str, wanted) -> dict:
-    """whole records of a file, streamed on the host (the fallback when the genome keeps no exception runs)"""
-    from . import fasta
-    out = {}
-    for i, rec in enumerate(fasta.StreamChunks(path, 0, 0)):
-        if i in wanted:
-            out[i] = bytes(rec.Seq)
-    return out
-
-
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="ipcr-hip", add_help=True)
     ap.add_argument("--primers", "-p", default="")
     ap.add_argument("--forward", "-f", default="")
     ap.add_argument("--reverse", "-r", default="")
-    ap.add_argument("--sequences", "-s", action="append", default=[])
-    ap.add_argument("--mismatches", "-m", type=int, default=0)
-    ap.add_argument("--min-length", type=int, default=0)
-    ap.add_argument("--max-length", type=int, default=2000)
-    ap.add_argument("--hit-cap", type=int, default=10000)
-    ap.add_argument("--terminal-window", type=int, default=3)
-    ap.add_argument("--self", dest="self_", action=argparse.BooleanOptionalAction, default=True)
-    ap.add_argument("--seed-length", type=int, default=12)
-    ap.add_argument("--circular", "-c", action="store_true")
-    ap.add_argument("--sort", action="store_true")
-    ap.add_argument("--output", "-o", default="text", choices=["text", "jsonl", "fasta"])
+    pipeline.add_common_flags(ap, dict(choices=["text", "jsonl", "fasta"]),
+                              "scan rolling chunks through ipcr_scan_chunk (0 = whole records resident)")
     ap.add_argument("--products", action="store_true", help="carry each product's sequence (JSONL field `seq`)")
-    ap.add_argument("--no-header", action="store_true")
     ap.add_argument("--multiplex", action="store_true", help="ipcr-multiplex self-pair rule (unique oligos)")
     ap.add_argument("--probe", "-P", default="")
     ap.add_argument("--probe-name", default="probe")
     ap.add_argument("--probe-max-mm", "-M", type=int, default=0)
     ap.add_argument("--require-probe", action=argparse.BooleanOptionalAction, default=True)
-    ap.add_argument("--no-match-exit-code", type=int, default=0)
-    ap.add_argument("--chunk-size", type=int, default=0, help="scan rolling chunks through ipcr_scan_chunk (0 = whole records resident)")
-    ap.add_argument("--dedup-cap", type=int, default=0)
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("fasta", nargs="*")
     return ap
 
 
@@ -260,158 +232,47 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
     if o.probe and need_seq:
         print("error: --probe does not support --products or --output fasta", file=stderr)
         return 2
-    tw = o.terminal_window if o.terminal_window >= 1 else 0            # runutil.EffectiveTerminalWindow
-    cfg = engine.Config(MaxMM=o.mismatches, TerminalWindow=tw, MinLen=o.min_length, MaxLen=o.max_length,
-                        HitCap=o.hit_cap, SeedLen=o.seed_length, Circular=o.circular)
-    _lib.check(_lib.lib().ipcr_set_device(o.device))
-    eng = engine.New(cfg)
+    eng = pipeline.new_engine(o, MinLen=o.min_length, MaxLen=o.max_length, HitCap=o.hit_cap, Circular=o.circular)
     cp = eng.CompilePanel(pairs)
     sc = eng.NewSimulationScratch(cp)
-    rows = []
     max_primer_len = max((max(len(p.Forward), len(p.Reverse)) for p in pairs), default=0)
-    chunk, overlap, warns = validate_chunking(o.circular, o.chunk_size, cfg.MaxLen, max_primer_len)
+    chunk, overlap, warns = validate_chunking(o.circular, o.chunk_size, o.max_length, max_primer_len)
     for w in warns:
         print(f"warning: {w}", file=stderr)
-    collector = Collector(o.dedup_cap)
-    for path in seq_files:
-        if chunk and not os.environ.get("IPCR_CLI_STREAM_CHUNKS"):
-            # --chunk-size from a resident genome: the file goes through the device loader, the tiles are swept ONCE, and
-            # every rolling window is joined as its own ForEachCompiledProduct call (ipcr_scan_genome_chunked) -- the same
-            # products, IDs and window-local coordinates as the stream below, which one thread parses at ~1 Gbases/s
-            size = os.path.getsize(path) if path != "-" and os.path.exists(path) else (1 << 28)
-            g = engine.Genome(max(size * (8 if path.endswith(".gz") else 1), 1 << 20), max_records=1 << 16)
-            try:
-                g.add_fasta(path)
-                prods = eng.ScanGenomeChunked(g, cp, sc, chunk, overlap)
-                probe_hits = [None] * len(prods)
-                if o.probe and prods:
-                    # ipcr-probe keeps --chunk-size (internal/probeapp/app.go:108): every product is annotated from its own
-                    # amplicon (the rescan reads it from the resident tiles: window-local coordinates are put back by the library)
-                    out = (_lib.ProbeHit * len(prods))()
-                    _lib.check(_lib.lib().ipcr_probe_products(sc._h, g._h, o.probe.encode(), o.probe_max_mm, out, len(prods)))
-                    probe_hits = [out[i] for i in range(len(prods))]
-                w, nw = C.POINTER(_lib.ChunkWindow)(), C.c_int64()
-                _lib.check(_lib.lib().ipcr_scratch_chunk_windows(sc._h, C.byref(w), C.byref(nw)))
-                seqs = [""] * len(prods)
-                if need_seq and prods:  # window-local coordinates -> the record's (ERR_UNSUPPORTED: stream the chunks)
-                    seqs = [_text(b) for b in g.read_windows([(w[p.Record].record, w[p.Record].start + p.Start,
-                                                                w[p.Record].start + p.End) for p in prods])]
-                for p, h, sq in zip(prods, probe_hits, seqs):
-                    ph = None
-                    if h is not None:
-                        if o.require_probe and not h.found:                 # internal/visitors/probe.go:20-22
-                            continue
-                        site = ""
-                        if h.found:
-                            cw = w[p.Record]
-                            amp = g.read(cw.record, cw.start + p.Start, p.End - p.Start)
-                            site = amp.upper()[h.pos:h.pos + len(primer.Normalize(o.probe))].decode()
-                        ph = (h, site)
-                    p = collector.add(path, p)
-                    if p is not None:
-                        rows.append((path, p, ph, sq))
-                g.close()
-                continue
-            except _lib.IpcrError as e:
-                g.close()
-                if e.status != _lib.ERR_UNSUPPORTED:                  # (a capped scan that ran in segments: stream the chunks)
-                    print(f"error: {e}", file=stderr)
-                    continue
-        if chunk:
-            # the reference's data path: every rolling chunk goes through the engine on its own
-            # (ForEachCompiledProduct = ipcr_scan_chunk), the collector restores record coordinates
-            from . import fasta
-            try:
-                for rec in fasta.StreamChunks(path, chunk, overlap):
-                    prods = eng.SimulateCompiledWithScratch(rec.ID, rec.Seq, cp, sc)
-                    # ipcr-probe keeps --chunk-size (internal/probeapp/app.go:108): the worker that scanned the chunk
-                    # annotates its products from the chunk's own tiles, chunk-local coordinates, before the
-                    # collector rebases them (pipeline.go:80-89 slices Product.Seq chunk-locally too)
-                    hits = sc.probe_products(o.probe, o.probe_max_mm) if o.probe and prods else [None] * len(prods)
-                    for p, h in zip(prods, hits):
-                        sq = _text(bytes(rec.Seq[p.Start:p.End])) if need_seq else ""
-                        ph = None
-                        if h is not None:
-                            if o.require_probe and not h.found:             # internal/visitors/probe.go:20-22
-                                continue
-                            site = ""
-                            if h.found:
-                                site = bytes(rec.Seq[p.Start:p.End]).upper()[h.pos:h.pos + len(primer.Normalize(o.probe))].decode()
-                            ph = (h, site)
-                        p = collector.add(path, p)
-                        if p is not None:
-                            rows.append((path, p, ph, sq))
-            except _lib.IpcrError as e:
-                print(f"error: {e}", file=stderr)
-            continue
-        size = os.path.getsize(path) if path != "-" and os.path.exists(path) else (1 << 28)
-        factor = 8 if path.endswith(".gz") else 1
-        g = engine.Genome(max(size * factor, 1 << 20), max_records=1 << 16)
-        try:
-            g.add_fasta(path)
-        except _lib.IpcrError as e:
-            print(f"error: {e}", file=stderr)       # pipeline.go:174-182: record the error, go on
-            continue
-        prods = eng.ScanGenome(g, cp, sc)
-        seqs = [""] * len(prods)
-        if need_seq and prods:
-            win = [(p.Record, p.Start, p.End) for p in prods]  # start > end: a product across the origin
-            try:
-                seqs = [_text(b) for b in g.read_windows(win)]
-            except _lib.IpcrError as e:
-                if e.status != _lib.ERR_UNSUPPORTED:
-                    raise
-                recs = _record_seqs(path, {r for r, _, _ in win})  # (the genome keeps no exception runs: stream the records)
-                seqs = [_text(recs[r][s:e] if s <= e else recs[r][s:] + recs[r][:e]) for r, s, e in win]
-        probe_hits = None
-        if o.probe:
-            out = (_lib.ProbeHit * max(len(prods), 1))()
-            _lib.check(_lib.lib().ipcr_probe_products(sc._h, g._h, o.probe.encode(), o.probe_max_mm, out, len(prods)))
-            probe_hits = [out[i] for i in range(len(prods))]
-        for i, p in enumerate(prods):
-            if probe_hits is None:
-                rows.append((path, p, None, seqs[i]))
-                continue
-            h = probe_hits[i]
-            if o.require_probe and not h.found:                         # internal/visitors/probe.go:20-22
-                continue
-            site = ""
-            if h.found:
-                amp = (g.read(p.Record, p.Start, p.End - p.Start) if p.Start <= p.End else
-                       g.read(p.Record, p.Start, g.record_len(p.Record) - p.Start) + g.read(p.Record, 0, p.End))
-                site = amp.upper()[h.pos:h.pos + len(primer.Normalize(o.probe))].decode()
-            rows.append((path, p, (h, site), ""))
-        g.close()
-    if not chunk:  # the collector sees every product in the reference, chunked or not (ids.go quirk included)
-        kept = []
-        for path, p, ph, sq in rows:
-            p = collector.add(path, p)
-            if p is not None:
-                kept.append((path, p, ph, sq))
-        rows = kept
+
+    def visit(b: pipeline.Batch) -> list:                               # (product, (probe hit, site) or None, seq)
+        seqs = [_text(a) for a in b.amplicons()] if need_seq else [""] * len(b.products)
+        if not o.probe:
+            return [(p, None, sq) for p, sq in zip(b.products, seqs)]
+        out = []
+        for i, h in enumerate(b.probe_hits(o.probe, o.probe_max_mm)):
+            if h.found or not o.require_probe:                          # internal/visitors/probe.go:20-22
+                site = b.probe_site(i, h.pos, len(primer.Normalize(o.probe))) if h.found else ""
+                out.append((b.products[i], (h, site), seqs[i]))
+        return out
+
+    # the collector sees every product in the reference, chunked or not (ids.go quirk included)
+    rows = pipeline.scan_files(seq_files, eng, cp, sc, chunk, overlap, Collector(o.dedup_cap), visit, stderr)
     if o.sort:
         rows.sort(key=lambda t: product_sort_key(t[0], t[1]))
     if o.output == "jsonl" and not o.probe:
         for path, p, _, sq in rows:
             print(format_jsonl(path, p, sq if o.products else ""), file=stdout)
-        return o.no_match_exit_code if (not rows and o.no_match_exit_code) else 0
-    if o.output == "fasta":
+    elif o.output == "fasta":
         for rec in fasta_records([(path, p, sq) for path, p, _, sq in rows], o.sort):
             print(rec, file=stdout)
-        return o.no_match_exit_code if (not rows and o.no_match_exit_code) else 0
-    if not o.no_header:
-        print(TSV_HEADER_PROBE if o.probe else TSV_HEADER, file=stdout)
-    for path, p, ph, _ in rows:
-        line = format_row(path, p)
-        if o.probe:                                                      # probeoutput/text.go:11-28
-            h, site = ph
-            line += "\t" + "\t".join([o.probe_name, o.probe.upper(), "true" if h.found else "false",
-                                      chr(h.strand) if h.found else "", str(h.pos) if h.found else "",
-                                      str(h.mm) if h.found else "", site])
-        print(line, file=stdout)
-    if not rows and o.no_match_exit_code:
-        return o.no_match_exit_code
-    return 0
+    else:
+        if not o.no_header:
+            print(TSV_HEADER_PROBE if o.probe else TSV_HEADER, file=stdout)
+        for path, p, ph, _ in rows:
+            line = format_row(path, p)
+            if o.probe:                                                  # probeoutput/text.go:11-28
+                h, site = ph
+                line += "\t" + "\t".join([o.probe_name, o.probe.upper(), "true" if h.found else "false",
+                                          chr(h.strand) if h.found else "", str(h.pos) if h.found else "",
+                                          str(h.mm) if h.found else "", site])
+            print(line, file=stdout)
+    return pipeline.exit_code(o, rows)
 
 
 if __name__ == "__main__":

@@ -244,13 +244,25 @@ class SimulationScratch:
         _lib.check(_lib.lib().ipcr_scratch_products(self._h, C.byref(ptr), C.byref(n)))
         return [_product(self._cp, ptr[i], seq_ids) for i in range(n.value)]
 
-    def probe_products(self, probe: str, max_mm: int):
-        """ipcr_probe_scratch_products: oligo.BestHit (core/oligo/oligo.go:19-77) for every product of the last
-        ipcr_scan_chunk on this scratch, rescanned from the chunk's own tiles -- what visitors.Probe.Visit computes
-        from Product.Seq (internal/visitors/probe.go:18-33).  List of _lib.ProbeHit, one per product."""
+    def chunk_windows(self) -> List[_lib.ChunkWindow]:
+        """ipcr_scratch_chunk_windows: the rolling windows of the last ipcr_scan_genome_chunked on this scratch; the
+        products of that scan carry the index of their window as Record and window-local coordinates."""
+        w, n = C.POINTER(_lib.ChunkWindow)(), C.c_int64()
+        _lib.check(_lib.lib().ipcr_scratch_chunk_windows(self._h, C.byref(w), C.byref(n)))
+        return w[:n.value]
+
+    def probe_products(self, probe: str, max_mm: int, genome: Optional["Genome"] = None):
+        """oligo.BestHit (core/oligo/oligo.go:19-77) for every product of the last scan on this scratch -- what
+        visitors.Probe.Visit computes from Product.Seq (internal/visitors/probe.go:18-33).  Without `genome` the scan
+        was an ipcr_scan_chunk and the amplicons are rescanned from the chunk's own tiles
+        (ipcr_probe_scratch_products); with it, from the resident tiles it scanned (ipcr_probe_products: window-local
+        coordinates are put back by the library).  List of _lib.ProbeHit, one per product."""
         n = self.num_products()
         out = (_lib.ProbeHit * max(n, 1))()
-        _lib.check(_lib.lib().ipcr_probe_scratch_products(self._h, probe.encode(), max_mm, out, n))
+        if genome is None:
+            _lib.check(_lib.lib().ipcr_probe_scratch_products(self._h, probe.encode(), max_mm, out, n))
+        else:
+            _lib.check(_lib.lib().ipcr_probe_products(self._h, genome._h, probe.encode(), max_mm, out, n))
         return [out[i] for i in range(n)]
 
 
@@ -487,10 +499,8 @@ class Engine:
         tiles.  Products carry window-local coordinates and the window's ID ('id:start-end', or the record's own ID when
         it never filled a window), exactly what fasta.StreamChunks + SimulateCompiledWithScratch give chunk by chunk."""
         _lib.check(_lib.lib().ipcr_scan_genome_chunked(cp._h, scratch._h, genome._h, chunkSize, overlap, None, None))
-        w, n = C.POINTER(_lib.ChunkWindow)(), C.c_int64()
-        _lib.check(_lib.lib().ipcr_scratch_chunk_windows(scratch._h, C.byref(w), C.byref(n)))
         ids = genome.ids
-        names = [ids[w[i].record] if w[i].plain else "%s:%d-%d" % (ids[w[i].record], w[i].start, w[i].end) for i in range(n.value)]
+        names = [ids[w.record] if w.plain else "%s:%d-%d" % (ids[w.record], w.start, w.end) for w in scratch.chunk_windows()]
         return scratch.products(names)
 
     def ScanGenomeCount(self, genome: Genome, cp: CompiledPanel, scratch: SimulationScratch) -> int:

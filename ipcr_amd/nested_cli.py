@@ -2,10 +2,8 @@
 internal/nestedcli/options.go:63-118 and the common flags of `ipcr_amd.cli`.
 
 Every outer product's amplicon is scanned with the inner panel on the device in one batch (ipcr_amd.nested); the
-best inner product follows internal/visitors/nested.go:35-51.  Three data paths, as in `cli.py`: whole records resident
-(ScanGenome + NestedProducts), `--chunk-size` over a resident genome (ScanGenomeChunked + NestedProducts) and, with
-IPCR_CLI_STREAM_CHUNKS=1, every rolling chunk through its worker's scratch (SimulateCompiledWithScratch +
-NestedScratchProducts).  Output: text (nestedoutput/text.go), jsonl and json (api.NestedProductV1, pkg/api/nested_v1.go);
+best inner product follows internal/visitors/nested.go:35-51.  The data paths are those of `ipcr_amd.pipeline`: NestedProducts
+over a resident genome (whole records or `--chunk-size`), NestedScratchProducts over a streamed chunk.  Output: text (nestedoutput/text.go), jsonl and json (api.NestedProductV1, pkg/api/nested_v1.go);
 `seq` is the outer amplicon's exact bytes, as NestedWriterFactory.NeedSeq() always asks for them.  --pretty is out of scope.
 
     python -m ipcr_amd.nested_cli --outer-primers O.tsv --inner-primers I.tsv --output jsonl --sort g.fa
@@ -13,14 +11,12 @@ NestedScratchProducts).  Output: text (nestedoutput/text.go), jsonl and json (ap
 from __future__ import annotations
 
 import argparse
-import ctypes as C
 import json
-import os
 import sys
 from typing import Optional, Sequence
 
-from . import _lib, engine, nested, primer
-from .cli import Collector, _record_seqs, _text, go_json_escape, load_tsv, product_sort_key, validate_chunking
+from . import nested, pipeline, primer
+from .cli import Collector, _text, go_json_escape, load_tsv, product_sort_key, validate_chunking
 
 TSV_HEADER_NESTED = ("source_file\tsequence_id\touter_experiment_id\touter_start\touter_end\touter_length\touter_type\t"
                      "inner_experiment_id\tinner_found\tinner_start\tinner_end\tinner_length\tinner_type\tinner_fwd_mm"
@@ -101,23 +97,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--inner-forward", "-F", default="")
     ap.add_argument("--inner-reverse", "-R", default="")
     ap.add_argument("--require-inner", action="store_true", help="only keep outer amplicons that contain an inner product")
-    ap.add_argument("--sequences", "-s", action="append", default=[])
-    ap.add_argument("--mismatches", "-m", type=int, default=0)
-    ap.add_argument("--min-length", type=int, default=0)
-    ap.add_argument("--max-length", type=int, default=2000)
-    ap.add_argument("--hit-cap", type=int, default=10000)
-    ap.add_argument("--terminal-window", type=int, default=3)
-    ap.add_argument("--self", dest="self_", action=argparse.BooleanOptionalAction, default=True)
-    ap.add_argument("--seed-length", type=int, default=12)
-    ap.add_argument("--circular", "-c", action="store_true")
-    ap.add_argument("--sort", action="store_true")
-    ap.add_argument("--output", "-o", default="text", help="text | json | jsonl")
-    ap.add_argument("--no-header", action="store_true")
-    ap.add_argument("--no-match-exit-code", type=int, default=0)
-    ap.add_argument("--chunk-size", type=int, default=0, help="scan rolling chunks (0 = whole records resident)")
-    ap.add_argument("--dedup-cap", type=int, default=0)
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("fasta", nargs="*")
+    pipeline.add_common_flags(ap, dict(help="text | json | jsonl"), "scan rolling chunks (0 = whole records resident)")
     return ap
 
 
@@ -172,10 +152,6 @@ def parse(argv: Optional[Sequence[str]]):
     return o, outer, inner
 
 
-def _stream_seq(seq: bytes, p: engine.Product) -> str:
-    return _text(bytes(seq[p.Start:p.End]) if p.Start <= p.End else bytes(seq[p.Start:]) + bytes(seq[:p.End]))
-
-
 def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
     """nestedapp.RunContext + appcore.Run (internal/appcore/core.go) for the scan path."""
     stdout = stdout or sys.stdout
@@ -202,68 +178,20 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
     chunk, overlap, warns = validate_chunking(o.circular, o.chunk_size, eff_max, max_primer_len)
     for w in warns:
         print(f"warning: {w}", file=stderr)
-    tw = o.terminal_window if o.terminal_window >= 1 else 0            # runutil.EffectiveTerminalWindow
-    _lib.check(_lib.lib().ipcr_set_device(o.device))
-    eng = engine.New(engine.Config(MaxMM=o.mismatches, TerminalWindow=tw, MinLen=o.min_length, MaxLen=o.max_length,
-                                   HitCap=o.hit_cap, SeedLen=o.seed_length, Circular=o.circular))
+    eng = pipeline.new_engine(o, MinLen=o.min_length, MaxLen=o.max_length, HitCap=o.hit_cap, Circular=o.circular)
     cp = eng.CompilePanel(outer_pairs)
     sc = eng.NewSimulationScratch(cp)
-    # the inner engine (app.go:154-165): linear amplicons, no length bounds, no hit cap
-    ieng = engine.New(engine.Config(MaxMM=o.mismatches, TerminalWindow=tw, SeedLen=o.seed_length, Circular=False))
+    ieng = pipeline.new_engine(o)       # the inner engine (app.go:154-165): linear amplicons, no length bounds, no hit cap
     cpi = ieng.CompilePanel(inner_pairs)
     sci = ieng.NewSimulationScratch(cpi)
-    collector = Collector(o.dedup_cap)
-    rows = []                                                           # (source_file, NestedProduct, seq)
 
-    def keep(path: str, np: nested.NestedProduct, seq: str) -> None:   # the collector, then visitors.Nested.Visit
-        p = collector.add(path, np.Product)
-        if p is not None and (np.InnerFound or not o.require_inner):
-            rows.append((path, np, seq))
+    def visit(b: pipeline.Batch) -> list:                               # (outer product, NestedProduct, seq)
+        return [(np.Product, np, _text(a)) for np, a in zip(b.nested(cpi, sci), b.amplicons())]
 
-    for path in o.seq_files:
-        size = os.path.getsize(path) if path != "-" and os.path.exists(path) else (1 << 28)
-        capacity = max(size * (8 if path.endswith(".gz") else 1), 1 << 20)
-        if not chunk or not os.environ.get("IPCR_CLI_STREAM_CHUNKS"):
-            # whole records, or --chunk-size over the resident genome (one sweep, every rolling window joined on its own)
-            g = engine.Genome(capacity, max_records=1 << 16)
-            try:
-                g.add_fasta(path)
-                prods = eng.ScanGenomeChunked(g, cp, sc, chunk, overlap) if chunk else eng.ScanGenome(g, cp, sc)
-                nps = nested.NestedProducts(sc, prods, g, cpi, sci)
-                win = [(p.Record, p.Start, p.End) for p in prods]
-                if chunk:                                               # window-local -> record coordinates
-                    w, nw = C.POINTER(_lib.ChunkWindow)(), C.c_int64()
-                    _lib.check(_lib.lib().ipcr_scratch_chunk_windows(sc._h, C.byref(w), C.byref(nw)))
-                    win = [(w[r].record, w[r].start + a, w[r].start + b) for r, a, b in win]
-                try:
-                    seqs = [_text(b) for b in g.read_windows(win)] if win else []
-                except _lib.IpcrError as e:
-                    if e.status != _lib.ERR_UNSUPPORTED:
-                        raise
-                    recs = _record_seqs(path, {r for r, _, _ in win})  # (no exception runs kept: stream the records)
-                    seqs = [_text(recs[r][a:b] if a <= b else recs[r][a:] + recs[r][:b]) for r, a, b in win]
-            except _lib.IpcrError as e:
-                g.close()
-                if not (chunk and e.status == _lib.ERR_UNSUPPORTED):    # (a capped scan that ran in segments: stream)
-                    print(f"error: {e}", file=stderr)               # pipeline.go:174-182: record the error, go on
-                    continue
-            else:
-                g.close()
-                for np, sq in zip(nps, seqs):
-                    keep(path, np, sq)
-                continue
-        # the reference's data path: every rolling chunk through the engine on its own; the worker that scanned the chunk
-        # scans its products' amplicons from the chunk's own tiles (pipeline.go:80-89 slices Product.Seq chunk-locally)
-        from . import fasta
-        try:
-            for rec in fasta.StreamChunks(path, chunk, overlap):
-                prods = eng.SimulateCompiledWithScratch(rec.ID, rec.Seq, cp, sc)
-                if not prods:
-                    continue
-                for np in nested.NestedScratchProducts(sc, prods, cpi, sci):
-                    keep(path, np, _stream_seq(rec.Seq, np.Product))
-        except _lib.IpcrError as e:
-            print(f"error: {e}", file=stderr)
+    # the collector, then visitors.Nested.Visit; rows: (source_file, NestedProduct, seq)
+    rows = [(path, np, sq) for path, _, np, sq in
+            pipeline.scan_files(o.seq_files, eng, cp, sc, chunk, overlap, Collector(o.dedup_cap), visit, stderr)
+            if np.InnerFound or not o.require_inner]
     if o.sort:
         rows = sort_rows(rows)
     if o.output == "json":
@@ -276,7 +204,7 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
             print(TSV_HEADER_NESTED, file=stdout)
         for path, np, _ in rows:
             print(format_row(path, np), file=stdout)
-    return o.no_match_exit_code if not rows else 0
+    return pipeline.exit_code(o, rows)
 
 
 if __name__ == "__main__":

@@ -174,6 +174,30 @@ def test_cli_end_to_end_matches_oracle(tmp_path, monkeypatch):
                 assert (r[14], r[15], r[16], r[17]) == (w.strand, str(w.pos), str(w.mm), w.site)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("path,site", [("whole", "GATTACAGNTCATGC"), ("chunk", "GATTACAGNTCATGC"),
+                                       ("chunk_stream", "GATTACAGRTCATGC")])
+def test_probe_site_with_an_iupac_code(tmp_path, monkeypatch, path, site):
+    """probe_site of a site that holds an IUPAC code: the resident paths cut it from the tiles read back (every byte outside
+    ACGT decodes as N), the streamed chunks from the chunk's own bytes -- pinned per path as it is today"""
+    import random
+    rng = random.Random(4)
+    fwd, rev = "ACGTTGCATGCAAGCT", "GGCCTTAAGGCCATAT"
+    pad = lambda n: "".join(rng.choice("ACGT") for _ in range(n))
+    amp = fwd + "TTGACCA" + "GATTACAGRTCATGC" + "CCATGGTA" + O.revcomp(rev).decode()
+    seq = pad(230) + amp + pad(400)
+    fa = tmp_path / "g.fa"
+    fa.write_text(">s\n%s\n" % "\n".join(seq[j:j + 60] for j in range(0, len(seq), 60)))
+    monkeypatch.setenv("IPCR_CLI_STREAM_CHUNKS", "1" if path == "chunk_stream" else "")
+    args = ["-f", fwd, "-r", rev, "--no-self", "--max-length", "100", "--probe", "GATTACAGGTCATGC", "--probe-max-mm", "1"]
+    out, err = io.StringIO(), io.StringIO()
+    assert cli.run(args + (["--chunk-size", "150"] if path != "whole" else []) + [str(fa)], stdout=out, stderr=err) == 0
+    assert err.getvalue() == ""
+    rows = [ln.split("\t") for ln in out.getvalue().splitlines()[1:]]
+    assert [r[1:6] + r[11:] for r in rows] == [
+        ["s", "manual", "230", "292", "62", "probe", "GATTACAGGTCATGC", "true", "+", "23", "1", site]]
+
+
 def test_chunking_rules():  # internal/runutil/runutil_test.go:20-59
     assert cli.compute_overlap(100, 21) == 100 and cli.compute_overlap(0, 21) == 20
     assert cli.validate_chunking(False, 0, 500, 25) == (0, 0, [])

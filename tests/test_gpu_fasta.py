@@ -280,3 +280,68 @@ def test_regular_files_are_packed_on_the_host_and_written_through_the_bar(tmp_pa
         check(tmp_path / "reg0.fa", False)
     finally:
         del os.environ["IPCR_FASTA_SLAB"]
+
+
+def _planted_file(path, seed, name):
+    import ipcr_oracle as O
+    fwd, rev = "ACGTTGCATGCAAGCTTA", "GGCCTTAAGGCCATATCG"
+    rc = O.revcomp(rev).decode()
+    s = list(O.bench_dna(30000, seed).decode())
+    for t in range(6):
+        a = 300 + t * 4900
+        s[a:a + len(fwd)] = fwd
+        s[a + 400 - len(rc):a + 400] = rc
+    s = "".join(s)
+    path.write_text(">%s\n%s\n" % (name, "\n".join(s[j:j + 60] for j in range(0, len(s), 60))))
+    return ["-f", fwd, "-r", rev, "-m", "1", "--max-length", "1000"]
+
+
+@pytest.mark.parametrize("mode", ["whole", "chunk", "chunk_stream"])
+def test_unreadable_file_between_two_good_ones(tmp_path, monkeypatch, mode):
+    """pipeline.go:174-182: a file that cannot be read is reported and the next one is scanned -- the rows of both good files,
+    one error line, exit 0, on every data path"""
+    monkeypatch.setenv("IPCR_CLI_STREAM_CHUNKS", "1" if mode == "chunk_stream" else "")
+    a, b, missing = tmp_path / "a.fa", tmp_path / "b.fa", tmp_path / "missing.fa"
+    base = _planted_file(a, 1, "ctgA")
+    _planted_file(b, 2, "ctgB")
+    base += ["--chunk-size", "5000"] if mode != "whole" else []
+    only_a, _ = _cli(base + [str(a)])
+    only_b, _ = _cli(base + [str(b)])
+    assert len(only_a.splitlines()) >= 7 and len(only_b.splitlines()) >= 7
+    out, err = _cli(base + [str(a), str(missing), str(b)])               # (_cli asserts exit 0)
+    assert out.splitlines() == only_a.splitlines() + only_b.splitlines()[1:]
+    assert [ln[:6] for ln in err.splitlines()] == ["error:"], err
+
+
+def test_chunked_scan_falls_back_to_streamed_chunks_after_a_segmented_capped_scan(tmp_path, monkeypatch):
+    """--chunk-size with a hit cap that bites on low-complexity records (those of test_hit_cap_bounds_device_memory): the capped
+    scan runs in segments, ipcr_scan_genome_chunked refuses (ERR_UNSUPPORTED) and the driver streams the chunks through
+    ipcr_scan_chunk instead -- the same output as IPCR_CLI_STREAM_CHUNKS=1.  (Not the unchunked output: a cap that bites applies
+    per window here and per record there.)"""
+    from ipcr_amd import _lib, engine, primer
+    monkeypatch.setenv("IPCR_TEST_HCAP_SOFT", "30000")
+    rng = random.Random(9)
+    fa = tmp_path / "polya.fa"
+    with open(fa, "wb") as fh:
+        for r in range(3):
+            s = bytearray(b"A" * 400_000)
+            for _ in range(40):
+                s[rng.randrange(len(s))] = rng.choice(b"CGTNn")
+            fh.write(b">r%d\n" % r + b"\n".join(s[j:j + 80] for j in range(0, len(s), 80)) + b"\n")
+    fwd, rev = "AAAAAAAAAAAA", "TTTTTTTTTTTT"
+    eng = engine.New(engine.Config(MaxMM=0, TerminalWindow=3, MaxLen=60, HitCap=50, SeedLen=12))
+    cp = eng.CompilePanel(primer.AddSelfPairs([primer.Pair("manual", fwd, rev, 0, 60)]))
+    sc = eng.NewSimulationScratch(cp)
+    g = engine.Genome(1 << 22, 4)
+    g.add_fasta(str(fa))
+    with pytest.raises(_lib.IpcrError) as e:                             # the branch under test is reached
+        eng.ScanGenomeChunked(g, cp, sc, 100_000, 60)
+    assert e.value.status == _lib.ERR_UNSUPPORTED
+    g.close(); sc.close(); cp.close()
+    base = ["-f", fwd, "-r", rev, "--hit-cap", "50", "--max-length", "60", "--chunk-size", "100000", str(fa)]
+    for extra in ([], ["--sort"]):
+        monkeypatch.setenv("IPCR_CLI_STREAM_CHUNKS", "")
+        got, err = _cli(base + extra)
+        monkeypatch.setenv("IPCR_CLI_STREAM_CHUNKS", "1")
+        want, _ = _cli(base + extra)
+        assert got == want and len(got.splitlines()) > 100 and err == "", extra

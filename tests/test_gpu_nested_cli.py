@@ -247,8 +247,7 @@ def _panels(circular=False):
 
 def test_nested_products_after_chunked_scan(files):
     """window-local products of ipcr_scan_genome_chunked are put back into their records before the gather"""
-    import ctypes as C
-    from ipcr_amd import _lib, engine, nested
+    from ipcr_amd import engine, nested
     _, recs = files
     g = engine.Genome(1 << 20, 8)
     for name, seq in recs:
@@ -260,8 +259,7 @@ def test_nested_products_after_chunked_scan(files):
             for p, n in zip(whole, nested.NestedProducts(sco, whole, g, cpi, sci))}
     chunked = oeng.ScanGenomeChunked(g, cpo, scc, 4000, 2000)
     got = nested.NestedProducts(scc, chunked, g, cpi, sci)
-    w, nw = C.POINTER(_lib.ChunkWindow)(), C.c_int64()
-    _lib.check(_lib.lib().ipcr_scratch_chunk_windows(scc._h, C.byref(w), C.byref(nw)))
+    w = scc.chunk_windows()
     assert len(chunked) > len(whole) >= 18       # products in the overlap of two windows come twice
     found = 0
     for p, n in zip(chunked, got):
@@ -344,3 +342,87 @@ def test_nested_scratch_products_errors_and_empty():
         nested.NestedScratchProducts(sco, [None], cpi, sci)
     g.close()
     host.close()
+
+
+def _nested_args(d):
+    return BASE_ARGS + ["--outer-primers", str(d / "outer.tsv"), "--inner-primers", str(d / "inner.tsv")]
+
+
+@pytest.mark.parametrize("mode", ["whole", "chunk", "chunk_stream"])
+def test_unreadable_file_between_two_good_ones(files, tmp_path, monkeypatch, mode):
+    """pipeline.go:174-182: a file that cannot be read is reported and the next one is scanned"""
+    from ipcr_amd import nested_cli
+    d, recs = files
+    monkeypatch.setenv("IPCR_CLI_STREAM_CHUNKS", "1" if mode == "chunk_stream" else "")
+    a, b = str(d / "g.fa"), str(tmp_path / "b.fa")
+    write_fa(b, recs[1:])
+    args = _nested_args(d) + (["--chunk-size", "4000"] if mode != "whole" else [])
+    only_a, only_b = run_cli(args + [a]), run_cli(args + [b])
+    assert len(only_a.splitlines()) >= 19 and len(only_b.splitlines()) >= 7
+    out, err = io.StringIO(), io.StringIO()
+    assert nested_cli.run(args + [a, str(tmp_path / "missing.fa"), b], stdout=out, stderr=err) == 0
+    assert out.getvalue().splitlines() == only_a.splitlines() + only_b.splitlines()[1:]
+    assert [ln[:6] for ln in err.getvalue().splitlines()] == ["error:"], err.getvalue()
+
+
+def test_chunked_scan_falls_back_to_streamed_chunks_after_a_segmented_capped_scan(tmp_path, monkeypatch):
+    """as the test of this name in test_gpu_fasta.py: ipcr_scan_genome_chunked refuses after a capped scan that ran in
+    segments, the driver streams the chunks -- the output of IPCR_CLI_STREAM_CHUNKS=1"""
+    from ipcr_amd import _lib, engine, primer
+    monkeypatch.setenv("IPCR_TEST_HCAP_SOFT", "30000")
+    rng = random.Random(9)
+    fa = tmp_path / "polya.fa"
+    recs = []
+    for r in range(3):
+        s = bytearray(b"A" * 400_000)
+        for _ in range(40):
+            s[rng.randrange(len(s))] = rng.choice(b"CGTNn")
+        recs.append(("r%d" % r, s.decode()))
+    write_fa(fa, recs)
+    fwd, rev = "AAAAAAAAAAAA", "TTTTTTTTTTTT"
+    eng = engine.New(engine.Config(MaxMM=0, TerminalWindow=3, MaxLen=60, HitCap=50, SeedLen=12))
+    cp = eng.CompilePanel(primer.AddSelfPairs([primer.Pair("outer", fwd, rev, 0, 60)]))
+    sc = eng.NewSimulationScratch(cp)
+    g = engine.Genome(1 << 22, 4)
+    g.add_fasta(str(fa))
+    with pytest.raises(_lib.IpcrError) as e:                             # the branch under test is reached
+        eng.ScanGenomeChunked(g, cp, sc, 100_000, 60)
+    assert e.value.status == _lib.ERR_UNSUPPORTED
+    g.close(); sc.close(); cp.close()
+    base = ["-f", fwd, "-r", rev, "-F", "AAAAAAAA", "-R", "TTTTTTTT", "--hit-cap", "50", "--max-length", "60",
+            "--chunk-size", "100000", "-o", "jsonl", str(fa)]
+    for extra in ([], ["--sort"]):
+        monkeypatch.setenv("IPCR_CLI_STREAM_CHUNKS", "")
+        got = run_cli(base + extra)
+        monkeypatch.setenv("IPCR_CLI_STREAM_CHUNKS", "1")
+        assert got == run_cli(base + extra) and len(got.splitlines()) > 100, extra
+    assert any(json.loads(ln)["inner_found"] for ln in got.splitlines())
+
+
+def test_sequences_from_a_genome_without_exception_runs(tmp_path, monkeypatch):
+    """a genome that kept no exception runs (IPCR_TEST_EXCEPTION_MAX lowers the bound): ipcr_genome_read_windows refuses and
+    `seq` comes from the file instead -- the same JSONL as with the runs kept, whole records and --chunk-size"""
+    from ipcr_amd import _lib, engine
+    rng = random.Random(31)
+    s = list(nested_record(rng))
+    for p in range(26_000, 30_000, 20):                                  # > 100 runs, behind the last amplicon
+        s[p] = "R"
+    fa = tmp_path / "g.fa"
+    write_fa(fa, [("chrA", "".join(s))])
+    write_tsv(tmp_path / "outer.tsv", [("O1", OUT_F, OUT_R, 0, 2000)])
+    write_tsv(tmp_path / "inner.tsv", INNER_TSV)
+    base = _nested_args(tmp_path) + ["-o", "jsonl", str(fa)]
+    forms = [[], ["--chunk-size", "4000"]]
+    monkeypatch.setenv("IPCR_CLI_STREAM_CHUNKS", "")
+    want = [run_cli(base + f) for f in forms]
+    assert all(len(w.splitlines()) >= 6 for w in want)
+    assert any(set(json.loads(ln)["seq"]) - set("ACGTN") for ln in want[0].splitlines())
+    monkeypatch.setenv("IPCR_TEST_EXCEPTION_MAX", "100")
+    g = engine.Genome(1 << 20, 4)
+    g.add_fasta(str(fa))
+    with pytest.raises(_lib.IpcrError) as e:                             # the branch under test is reached
+        g.read_windows([(0, 0, 10)])
+    assert e.value.status == _lib.ERR_UNSUPPORTED
+    g.close()
+    for f, w in zip(forms, want):
+        assert run_cli(base + f) == w, f

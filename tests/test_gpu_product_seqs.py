@@ -81,8 +81,7 @@ def test_scan_genome_products_exact():
 
 
 def test_scan_genome_chunked_products_exact():
-    import ctypes as C
-    from ipcr_amd import _lib, engine
+    from ipcr_amd import engine
     rng = random.Random(2)
     recs = [amplicon_record(rng, 4, 40_000), amplicon_record(rng, 2, 20_000)]
     g = engine.Genome(200_000, 4)
@@ -90,8 +89,7 @@ def test_scan_genome_chunked_products_exact():
         g.add_record("r%d" % i, r)
     eng, cp, sc = engine_for()
     prods = eng.ScanGenomeChunked(g, cp, sc, 3000, 2000)
-    w, nw = C.POINTER(_lib.ChunkWindow)(), C.c_int64()
-    _lib.check(_lib.lib().ipcr_scratch_chunk_windows(sc._h, C.byref(w), C.byref(nw)))
+    w = sc.chunk_windows()
     win = [(w[p.Record].record, w[p.Record].start + p.Start, w[p.Record].start + p.End) for p in prods]
     assert len(win) >= 6
     got = g.read_windows(win)
@@ -178,3 +176,34 @@ def test_cli_products_jsonl_and_text(tmp_path):
         assert seq.encode() == recs[0][da["start"]:da["end"]]
         assert list(json.loads(b).keys())[-2:] == ["seq", "source_file"]
     assert cli(args) == cli(args + ["--products"])
+
+
+def test_cli_sequences_from_a_genome_without_exception_runs(tmp_path, monkeypatch):
+    """A genome with more runs of bytes outside ACGTacgtN than its bound keeps none (IPCR_TEST_EXCEPTION_MAX lowers the bound)
+    and ipcr_genome_read_windows refuses: the driver takes the amplicon bytes from the file instead -- the same output as
+    with the runs kept, whole records and --chunk-size."""
+    from ipcr_amd import _lib, engine
+    rng = random.Random(12)
+    recs = []
+    for n_amp, length in ((4, 40_000), (2, 20_000)):
+        s = bytearray(amplicon_record(rng, n_amp, length))
+        for p in range(length * 3 // 4, length, 50):                     # > 100 runs, behind the last amplicon
+            s[p] = ord("R")
+        recs.append(bytes(s))
+    fa = tmp_path / "g.fa"
+    write_fa(fa, recs)
+    base = ["-f", FW, "-r", RV, "-m", "3", "--terminal-window", "0", "--min-length", "50", str(fa)]
+    forms = [out + chunk for out in (["-o", "jsonl", "--products"], ["-o", "fasta"]) for chunk in ([], ["--chunk-size", "3000"])]
+    monkeypatch.setenv("IPCR_CLI_STREAM_CHUNKS", "")
+    want = [cli(base + f) for f in forms]
+    assert all(len(w.splitlines()) >= 6 for w in want)
+    assert set("".join(want[2].splitlines()[1::2])) - set("ACGTN"), "no byte outside ACGTN inside the products"
+    monkeypatch.setenv("IPCR_TEST_EXCEPTION_MAX", "100")
+    g = engine.Genome(1 << 20, 4)
+    g.add_fasta(str(fa))
+    with pytest.raises(_lib.IpcrError) as e:                             # the branch under test is reached
+        g.read_windows([(0, 0, 10)])
+    assert e.value.status == _lib.ERR_UNSUPPORTED
+    g.close()
+    for f, w in zip(forms, want):
+        assert cli(base + f) == w, f

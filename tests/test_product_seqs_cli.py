@@ -51,3 +51,35 @@ def test_probe_with_sequences_is_refused(tmp_path):
         rc = cli.run(["-f", "ACGTACGTAC", "-r", "ACGTACGTAC", "--probe", "ACGTAC", *extra, str(fa)], stdout=out, stderr=err)
         assert rc == 2, extra
         assert "--probe" in err.getvalue()
+
+
+def test_both_drivers_take_the_common_flags_with_the_same_defaults():
+    """internal/clibase/common.go:61-110: one set of common flags under ipcr, ipcr-probe, ipcr-multiplex and ipcr-nested"""
+    from ipcr_amd import nested_cli
+    common = [  # (flag, short form, destination, default, a value to parse, what it parses to)
+        ("--sequences", "-s", "sequences", [], "a.fa", ["a.fa"]),
+        ("--mismatches", "-m", "mismatches", 0, "2", 2),
+        ("--min-length", None, "min_length", 0, "5", 5),
+        ("--max-length", None, "max_length", 2000, "50", 50),
+        ("--hit-cap", None, "hit_cap", 10000, "7", 7),
+        ("--terminal-window", None, "terminal_window", 3, "-1", -1),
+        ("--no-self", None, "self_", True, None, False),
+        ("--self", None, "self_", True, None, True),
+        ("--seed-length", None, "seed_length", 12, "8", 8),
+        ("--circular", "-c", "circular", False, None, True),
+        ("--sort", None, "sort", False, None, True),
+        ("--output", "-o", "output", "text", "jsonl", "jsonl"),
+        ("--no-header", None, "no_header", False, None, True),
+        ("--no-match-exit-code", None, "no_match_exit_code", 0, "7", 7),
+        ("--chunk-size", None, "chunk_size", 0, "4000", 4000),
+        ("--dedup-cap", None, "dedup_cap", 0, "9", 9),
+        ("--device", None, "device", 0, "1", 1),
+    ]
+    for build in (cli.build_parser, nested_cli.build_parser):
+        defaults = vars(build().parse_args([]))
+        assert defaults["fasta"] == []
+        for flag, short, dest, default, text, value in common:
+            assert defaults[dest] == default, (build.__module__, flag)
+            for name in filter(None, (flag, short)):
+                o = build().parse_args([name] + ([text] if text is not None else []) + ["x.fa", "y.fa"])
+                assert getattr(o, dest) == value and o.fasta == ["x.fa", "y.fa"], (build.__module__, name)
