@@ -37,8 +37,9 @@ typedef enum {
     IPCR_ERR_ABORTED = 6      /* emit callback returned non-zero (ForEachCompiledProduct's emit error) */
 } ipcr_status;
 
-/* engine.Config -- core/engine/engine.go:10-19.  need_sites only affects presentation
- * (FwdSite/RevSite) and is ignored by the scan. */
+/* engine.Config -- core/engine/engine.go:10-19.  need_sites does not change what a scan finds: ipcr_product carries no
+ * site strings.  A caller that wants FwdSite / RevSite (engine.go:177-185) asks for them after the scan: ipcr_product_sites
+ * over a resident genome; after ipcr_scan_chunk it slices the chunk it holds. */
 typedef struct {
     int32_t max_mm;
     int32_t terminal_window;
@@ -447,6 +448,34 @@ ipcr_status ipcr_nested_windows(const ipcr_genome *g, const ipcr_window *windows
  * exception runs (more than its bound).  Safe from several threads at once, next to scans on other scratches. */
 ipcr_status ipcr_genome_read_windows(const ipcr_genome *g, const ipcr_window *windows, int64_t n, uint8_t *out,
                                      uint64_t cap, uint64_t *offsets, uint64_t *needed);
+/* exact bytes of n short sites of a resident genome, packed: site i is out[offsets[i] .. offsets[i+1]) (offsets: n + 1
+ * entries, nothing is padded).  A site is `len` (1 .. IPCR_MAX_PRIMER_LEN) consecutive bases of `record` from `pos`; it never
+ * wraps (a primer does not span the origin, core/engine/engine.go:242-249).  revcomp != 0: the site comes back reverse-
+ * complemented on the device, with the table of core/primer/rc.go:8-24 (upper-case IUPAC DNA).  The bytes are the record as
+ * loaded, as ipcr_genome_read_windows returns them -- that call gives a workgroup to every window; this one packs 256 sites
+ * into a workgroup and takes one launch per 2^21 sites or 64 MiB of output.  *needed = total bytes; IPCR_ERR_CAPACITY (offsets
+ * and *needed written, out untouched) when cap < *needed; IPCR_ERR_INVALID for a site outside its record, len == 0 or
+ * len > IPCR_MAX_PRIMER_LEN; IPCR_ERR_UNSUPPORTED when the genome dropped its exception runs; IPCR_ERR_PRIMER when a
+ * reverse-complemented site holds a byte without a complement (lower case, '-', '*', 'U', ...: RevComp panics there,
+ * rc.go:28-33) -- ipcr_last_error names the first such site, its record, the position and the byte; out is then undefined.
+ * n == 0 is IPCR_OK.  Safe from several threads at once, next to scans on other scratches. */
+typedef struct ipcr_site {
+    int64_t pos;
+    int32_t record;
+    uint16_t len;
+    uint16_t revcomp;
+} ipcr_site;
+ipcr_status ipcr_genome_read_sites(const ipcr_genome *g, const ipcr_site *sites, int64_t n, uint8_t *out, uint64_t cap,
+                                   uint64_t *offsets, uint64_t *needed);
+/* FwdSite / RevSite of every product of the last scan on `s` over the resident genome `g` (engine.go:177-185, :242-250,
+ * :308-316, :372-380): sites 2 i and 2 i + 1 of the packed output belong to product i (offsets: 2 n_products + 1 entries).
+ * FwdSite = the bases under the product's left primer at `start`; RevSite = the reverse complement of the bases under its
+ * right primer, which end at `end`; the left primer of a revcomp product is the pair's reverse primer (engine.go:326-331).
+ * After ipcr_scan_genome_chunked the products' window-local coordinates are put back into their records first (the bytes are
+ * the same: a window is a slice of its record).  Errors as ipcr_genome_read_sites; IPCR_ERR_INVALID also when n_products
+ * differs from the scratch's product count or the last scan was an ipcr_scan_chunk (its caller holds the chunk's bytes). */
+ipcr_status ipcr_product_sites(const ipcr_scratch *s, const ipcr_genome *g, uint8_t *out, uint64_t cap,
+                               uint64_t *offsets /* 2 n_products + 1 */, int64_t n_products, uint64_t *needed);
 /* runs of bytes outside ACGTacgtN the genome keeps (UINT64_MAX: dropped, see above) */
 uint64_t ipcr_genome_exception_runs(const ipcr_genome *g);
 /* every product of the last scan on `outer` over the resident genome `g` (out[i] <-> product i).  After

@@ -60,6 +60,11 @@ class Window(C.Structure):
     _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("record", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Site(C.Structure):
+    """ipcr_site: `len` bases of `record` from `pos`, reverse-complemented on the device when `revcomp`"""
+    _fields_ = [("pos", C.c_int64), ("record", C.c_int32), ("len", C.c_uint16), ("revcomp", C.c_uint16)]
+
+
 class NestedHit(C.Structure):
     _fields_ = [("found", C.c_int32), ("pair", C.c_int32), ("type", C.c_int32), ("fwd_mm", C.c_int32),
                 ("rev_mm", C.c_int32), ("reserved", C.c_int32), ("start", C.c_int64), ("end", C.c_int64),
@@ -126,6 +131,10 @@ SYMBOLS = {
     "ipcr_genome_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_char_p, C.c_uint64]),
     "ipcr_genome_read_windows": (C.c_int, [C.c_void_p, C.POINTER(Window), C.c_int64, C.c_void_p, C.c_uint64,
                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ipcr_genome_read_sites": (C.c_int, [C.c_void_p, C.POINTER(Site), C.c_int64, C.c_void_p, C.c_uint64,
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ipcr_product_sites": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int64,
+                                     C.POINTER(C.c_uint64)]),
     "ipcr_genome_exception_runs": (C.c_uint64, [C.c_void_p]),
     "ipcr_genome_num_records": (C.c_uint32, [C.c_void_p]),
     "ipcr_genome_record_len": (C.c_uint64, [C.c_void_p, C.c_uint32]),

@@ -4,8 +4,9 @@ Only what sits directly either side of the scan path ("nex
 FASTA -> resident tiles, the collector's total product order, and the text/TSV rows -- with the
 reference's flag names and defaults (internal/clibase/common.go:61-110) so outputs can be
 diffed against `ipcr`.  --products (JSONL `seq`) and --output fasta carry the amplicon bytes, read exactly from the
-resident genome (ipcr_genome_read_windows).  The data paths (resident, --chunk-size, streamed chunks) are `ipcr_amd.pipeline`.  Thermo scoring, pretty blocks and JSON are out of scope; nested PCR
-is `ipcr_amd.nested_cli`.
+resident genome (ipcr_genome_read_windows).  The data paths (resident, --chunk-size, streamed chunks) are `ipcr_amd.pipeline`.  --pretty writes the alignment block of
+`ipcr_amd.pretty` under every text row, from sites the device read (ipcr_product_sites).  Thermo scoring and the JSON
+array are out of scope; nested PCR is `ipcr_amd.nested_cli`.
 
     python -m ipcr_amd.cli -f AGAGTTTGATCMTGGCTCAG -r TACGGYTACCTTGTTAYGACTT --mismatches 0 demo.fa
 """
@@ -15,7 +16,7 @@ import argparse
 import sys
 from typing import List, Optional, Sequence
 
-from . import engine, pipeline, primer
+from . import engine, pipeline, pretty, primer
 
 TSV_HEADER = ("source_file\tsequence_id\texperiment_id\tstart\tend\tlength\ttype\tfwd_mm\trev_mm"
               "\tfwd_mm_i\trev_mm_i")                                   # internal/output/common.go:5
@@ -205,6 +206,17 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def engine_config(o) -> engine.Config:
+    """the engine's configuration for parsed options; NeedSites only when the block will be written: text output and
+    --pretty (internal/appcore/writer_factories.go:36-38)"""
+    return pipeline.engine_config(o, **_bounds(o))
+
+
+def _bounds(o) -> dict:
+    return dict(MinLen=o.min_length, MaxLen=o.max_length, HitCap=o.hit_cap, Circular=o.circular,
+                NeedSites=pipeline.want_pretty(o))
+
+
 def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
     """app.RunContext -- internal/app/app.go:23-114 (scan-relevant part)."""
     stdout = stdout or sys.stdout
@@ -232,7 +244,7 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
     if o.probe and need_seq:
         print("error: --probe does not support --products or --output fasta", file=stderr)
         return 2
-    eng = pipeline.new_engine(o, MinLen=o.min_length, MaxLen=o.max_length, HitCap=o.hit_cap, Circular=o.circular)
+    eng = pipeline.new_engine(o, **_bounds(o))
     cp = eng.CompilePanel(pairs)
     sc = eng.NewSimulationScratch(cp)
     max_primer_len = max((max(len(p.Forward), len(p.Reverse)) for p in pairs), default=0)
@@ -264,14 +276,21 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
     else:
         if not o.no_header:
             print(TSV_HEADER_PROBE if o.probe else TSV_HEADER, file=stdout)
+        show = pipeline.want_pretty(o)
         for path, p, ph, _ in rows:
             line = format_row(path, p)
+            block = pretty.render_product(p) if show else ""           # internal/output/text.go:21-30
             if o.probe:                                                  # probeoutput/text.go:11-28
                 h, site = ph
                 line += "\t" + "\t".join([o.probe_name, o.probe.upper(), "true" if h.found else "false",
                                           chr(h.strand) if h.found else "", str(h.pos) if h.found else "",
                                           str(h.mm) if h.found else "", site])
+                if show:                                                 # probeoutput/pretty.go: the row's own fields
+                    block = pretty.render_annotated(p, pretty.ProbeAnnotation(
+                        Name=o.probe_name, Seq=o.probe.upper(), Found=bool(h.found), Strand=chr(h.strand) if h.found else "",
+                        Pos=h.pos if h.found else 0, MM=h.mm if h.found else 0, Site=site))
             print(line, file=stdout)
+            pipeline.write_text(stdout, block)
     return pipeline.exit_code(o, rows)
 
 

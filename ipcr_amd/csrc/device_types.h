@@ -48,6 +48,14 @@ struct ipcr_exc_run {
     uint8_t byte, pad[3];
 };
 
+// one short site of a read piece (ipcr_genome_read_sites): `len` (1..128) bases from padded position P, written to
+// out[off, off + len) -- reverse-complemented when rc.  A piece's sites are in output order: off ascending, no gaps.
+struct ipcr_site_dev {
+    uint64_t P;
+    uint32_t off;
+    uint16_t len, rc;
+};
+
 struct ipcr_probe_rec { // layout-identical to ipcr_probe_hit
     int32_t found, strand, pos, mm;
 };

@@ -1785,11 +1785,16 @@ namespace {
 constexpr uint64_t READ_PIECE_BYTES = 64ull << 20;  // output bytes per gather launch
 constexpr uint64_t READ_PIECE_SEGS = 1ull << 18;    // segments per gather launch
 constexpr uint64_t READ_SEG_BYTES = 16384;          // a longer window is cut into segments of this size (one workgroup each)
+constexpr uint64_t READ_PIECE_SITES = 1ull << 21;   // sites per launch of the site read (IPCR_TEST_SITE_PIECE lowers it)
 struct ReadCtx {
     int slot = 0;
     hipStream_t st = nullptr;
     uint8_t *d_out = nullptr;
     ipcr_amp_seg *d_segs = nullptr, *h_segs = nullptr; // h_segs pinned
+    // ipcr_genome_read_sites (allocated by its first call on this context): the sites of one piece, and the word its
+    // kernel reports a byte without a complement through
+    ipcr_site_dev *d_sites = nullptr, *h_sites = nullptr; // h_sites pinned
+    unsigned long long *d_bad = nullptr, *h_bad = nullptr; // h_bad pinned
 };
 std::mutex g_read_mu;
 std::vector<ReadCtx *> g_read_free;
@@ -1891,6 +1896,108 @@ ipcr_status ipcr_genome_read_windows(const ipcr_genome *cg, const ipcr_window *w
     read_ctx_release(c);
     HIPCHK(e);
     return IPCR_OK;
+}
+
+} // extern "C"
+
+namespace {
+
+// the site read's buffers of a context, made once
+ipcr_status read_ctx_site_buffers(ReadCtx *c) {
+    if (c->d_sites) return IPCR_OK;
+    ipcr_site_dev *d = nullptr, *h = nullptr;
+    unsigned long long *db = nullptr, *hb = nullptr;
+    hipError_t e = hipMalloc((void **)&d, READ_PIECE_SITES * sizeof(ipcr_site_dev));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&h, READ_PIECE_SITES * sizeof(ipcr_site_dev), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void **)&db, 8);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&hb, 8, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        if (db) (void)hipFree(db);
+        if (hb) (void)hipHostFree(hb);
+        return fail(IPCR_ERR_DEVICE, "ipcr_genome_read_sites: %s", hipGetErrorString(e));
+    }
+    c->d_sites = d; c->h_sites = h; c->d_bad = db; c->h_bad = hb;
+    return IPCR_OK;
+}
+
+// ipcr_genome_read_sites / ipcr_product_sites (`what` names the caller in messages)
+ipcr_status read_sites(const char *what, ipcr_genome *g, const ipcr_site *sites, int64_t n, uint8_t *out, uint64_t cap,
+                       uint64_t *offsets, uint64_t *needed) {
+    offsets[0] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const ipcr_site &s = sites[i];
+        if (s.record < 0 || (size_t)s.record >= g->rec_len.size()) return fail(IPCR_ERR_INVALID, "%s: site %lld: no record %d", what, (long long)i, s.record);
+        if (s.len == 0 || s.len > IPCR_MAX_PRIMER_LEN)
+            return fail(IPCR_ERR_INVALID, "%s: site %lld: length %u is not in 1..%d", what, (long long)i, (unsigned)s.len, IPCR_MAX_PRIMER_LEN);
+        const int64_t L = (int64_t)g->rec_len[(size_t)s.record];
+        if (s.pos < 0 || s.pos > L || (int64_t)s.len > L - s.pos)
+            return fail(IPCR_ERR_INVALID, "%s: site %lld [%lld, %lld) outside its record of %lld bases", what, (long long)i, (long long)s.pos,
+                        (long long)s.pos + s.len, (long long)L);
+        offsets[i + 1] = offsets[i] + s.len;
+    }
+    *needed = offsets[n];
+    if (cap < *needed) return fail(IPCR_ERR_CAPACITY, "%s: %llu bytes do not fit %llu", what, (unsigned long long)*needed, (unsigned long long)cap);
+    if (n == 0) return IPCR_OK;
+    DeviceGuard dg(g->device);
+    uint64_t nruns = 0;
+    {
+        std::lock_guard<std::mutex> lk(g->read_mu);
+        const ipcr_status st = genome_finalize(g);
+        if (st != IPCR_OK) return st;
+        if (g->exc_dropped) return fail(IPCR_ERR_UNSUPPORTED, "%s: the genome holds more than %llu exception runs and keeps none", what,
+                                        (unsigned long long)g->exc_bound);
+        if (!g->exc_capture) return fail(IPCR_ERR_UNSUPPORTED, "%s: a scratch-private genome keeps no exception runs", what);
+        nruns = g->exc_sorted;
+    }
+    if (!out) return fail(IPCR_ERR_INVALID, "%s: null output", what);
+    uint64_t piece_sites = READ_PIECE_SITES;
+    if (const char *e = getenv("IPCR_TEST_SITE_PIECE"))
+        if (*e) piece_sites = std::min<uint64_t>(piece_sites, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
+    ReadCtx *c = nullptr;
+    ipcr_status st = read_ctx_acquire(g->device, &c);
+    if (st != IPCR_OK) return st;
+    st = read_ctx_site_buffers(c);
+    hipError_t e = hipSuccess;
+    // pieces of consecutive sites: at most piece_sites of them and READ_PIECE_BYTES of output, one launch each
+    for (int64_t i0 = 0; i0 < n && st == IPCR_OK && e == hipSuccess;) {
+        uint64_t m = 0, bytes = 0;
+        for (; i0 + (int64_t)m < n && m < piece_sites && bytes + sites[i0 + (int64_t)m].len <= READ_PIECE_BYTES; ++m) {
+            const ipcr_site &s = sites[i0 + (int64_t)m];
+            c->h_sites[m] = ipcr_site_dev{g->rec_start[(size_t)s.record] + (uint64_t)s.pos, (uint32_t)bytes, s.len, (uint16_t)(s.revcomp ? 1 : 0)};
+            bytes += s.len;
+        }
+        *c->h_bad = ~0ull;
+        e = hipMemcpyAsync(c->d_bad, c->h_bad, 8, hipMemcpyHostToDevice, c->st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->d_sites, c->h_sites, m * sizeof(ipcr_site_dev), hipMemcpyHostToDevice, c->st);
+        if (e == hipSuccess) e = ipcr::launch_read_sites(c->st, g->planes, g->rst, c->d_sites, (uint32_t)m, c->d_out, g->d_exc, nruns, c->d_bad);
+        if (e == hipSuccess) e = hipMemcpyAsync(out + offsets[i0], c->d_out, bytes, hipMemcpyDeviceToHost, c->st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->h_bad, c->d_bad, 8, hipMemcpyDeviceToHost, c->st);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->st); // (h_sites, d_out and the word are reused by the next piece)
+        if (e == hipSuccess && *c->h_bad != ~0ull) {
+            const unsigned long long v = *c->h_bad;
+            const int64_t i = i0 + (int64_t)(v >> 16);
+            const unsigned off = (unsigned)((v >> 8) & 0xFFu), b = (unsigned)(v & 0xFFu);
+            st = fail(IPCR_ERR_PRIMER, "%s: site %lld (record %d, position %lld): byte 0x%02x%s%c%s has no reverse complement "
+                      "(upper-case IUPAC DNA only, core/primer/rc.go:8-24)", what, (long long)i, sites[i].record, (long long)sites[i].pos + off, b,
+                      (b >= 0x21 && b < 0x7F) ? " '" : "", (b >= 0x21 && b < 0x7F) ? (char)b : ' ', (b >= 0x21 && b < 0x7F) ? "'" : "");
+        }
+        i0 += (int64_t)m;
+    }
+    read_ctx_release(c);
+    if (st != IPCR_OK) return st;
+    HIPCHK(e);
+    return IPCR_OK;
+}
+} // namespace
+
+extern "C" {
+
+ipcr_status ipcr_genome_read_sites(const ipcr_genome *cg, const ipcr_site *sites, int64_t n, uint8_t *out, uint64_t cap,
+                                   uint64_t *offsets, uint64_t *needed) {
+    if (!cg || n < 0 || (n && !sites) || !offsets || !needed) return fail(IPCR_ERR_INVALID, "ipcr_genome_read_sites: null argument");
+    return read_sites("ipcr_genome_read_sites", const_cast<ipcr_genome *>(cg), sites, n, out, cap, offsets, needed);
 }
 
 uint64_t ipcr_genome_exception_runs(const ipcr_genome *cg) {
@@ -4117,6 +4224,30 @@ ipcr_status ipcr_nested_products(const ipcr_scratch *outer, const ipcr_genome *g
     if ((int64_t)n != n_out) return fail(IPCR_ERR_INVALID, "n_out (%lld) != products of the last scan (%zu)", (long long)n_out, n);
     const std::vector<ipcr_window> w = outer_windows(outer, outer->products_in_windows);
     return nested_run(g, w.data(), (int64_t)n, inner, s, out);
+}
+
+// FwdSite / RevSite of the products of the last scan on `s` (core/engine/engine.go:177-185, :242-250, :308-316, :372-380):
+// the bases under the product's left primer at `start`, and the reverse complement of those under its right primer, which
+// end at `end` -- also for a wrap-around product, whose primers never span the origin.  A revcomp product's left primer is
+// the pair's Reverse (engine.go:326-331).
+ipcr_status ipcr_product_sites(const ipcr_scratch *s, const ipcr_genome *g, uint8_t *out, uint64_t cap, uint64_t *offsets,
+                               int64_t n_products, uint64_t *needed) {
+    if (!s || !g || !offsets || !needed) return fail(IPCR_ERR_INVALID, "ipcr_product_sites: null argument");
+    const size_t n = s->products.size();
+    if ((int64_t)n != n_products) return fail(IPCR_ERR_INVALID, "ipcr_product_sites: n_products (%lld) != products of the last scan (%zu)", (long long)n_products, n);
+    if (n && s->last_was_chunk)
+        return fail(IPCR_ERR_INVALID, "ipcr_product_sites: the last scan was an ipcr_scan_chunk, whose caller holds the chunk's bytes");
+    const std::vector<ipcr_window> w = outer_windows(s, s->products_in_windows);
+    std::vector<ipcr_site> sites(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const ipcr_product &pr = s->products[i];
+        if (pr.pair < 0 || (size_t)pr.pair >= s->panel->fwd.size()) return fail(IPCR_ERR_INVALID, "ipcr_product_sites: product %zu: no pair %d", i, pr.pair);
+        const size_t fl = s->panel->fwd[(size_t)pr.pair].size(), rl = s->panel->rev[(size_t)pr.pair].size();
+        const size_t left = pr.type == 0 ? fl : rl, right = pr.type == 0 ? rl : fl;
+        sites[2 * i] = ipcr_site{w[i].start, w[i].record, (uint16_t)left, 0};
+        sites[2 * i + 1] = ipcr_site{w[i].end - (int64_t)right, w[i].record, (uint16_t)right, 1};
+    }
+    return read_sites("ipcr_product_sites", const_cast<ipcr_genome *>(g), sites.data(), (int64_t)(2 * n), out, cap, offsets, needed);
 }
 
 // ipcr-nested on a worker: the products of the outer scratch's last ipcr_scan_chunk, their amplicons read from the tiles

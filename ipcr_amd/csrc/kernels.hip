@@ -751,6 +751,89 @@ __global__ __launch_bounds__(256) void gather_amplicons_kernel(const uint32_t *_
     }
 }
 
+// short sites (ipcr_genome_read_sites): a workgroup takes IPCR_SITE_GROUP consecutive sites, whose output bytes are
+// consecutive too.  It stages the sites in LDS; a lane then decodes four consecutive output bytes and stores them as one
+// dword, finding the site of its first byte by a binary search of the group's output offsets in LDS (byte stores only in
+// the group's partial first / last dword, which the neighbouring group shares).  A byte that decodes as 'N' (inv and rst
+// both set) is looked up in the genome's run list -- no other byte is; a genome without runs passes none.  A site with rc
+// set is read backwards and complemented with the table of core/primer/rc.go:8-24; a byte that table does not hold goes out
+// as it is and is reported through *bad: the smallest (site << 16 | offset in the record's direction << 8 | byte) wins,
+// so the host learns the first offending site and, inside it, the byte RevCompStrict would have met first.
+#define IPCR_SITE_GROUP 256u
+__device__ __forceinline__ uint32_t site_complement(uint32_t b) {
+    switch (b) {
+    case 'A': return 'T';
+    case 'C': return 'G';
+    case 'G': return 'C';
+    case 'T': return 'A';
+    case 'R': return 'Y';
+    case 'Y': return 'R';
+    case 'S': return 'S';
+    case 'W': return 'W';
+    case 'K': return 'M';
+    case 'M': return 'K';
+    case 'B': return 'V';
+    case 'V': return 'B';
+    case 'D': return 'H';
+    case 'H': return 'D';
+    case 'N': return 'N';
+    default: return 0u;
+    }
+}
+__global__ __launch_bounds__(256) void read_sites_kernel(const uint32_t *__restrict__ planes, const uint32_t *__restrict__ rst,
+                                                         const ipcr_site_dev *__restrict__ sites, uint32_t nsites,
+                                                         uint8_t *__restrict__ out, const ipcr_exc_run *__restrict__ runs,
+                                                         uint64_t nruns, unsigned long long *__restrict__ bad) {
+    __shared__ ipcr_site_dev s_site[IPCR_SITE_GROUP];
+    __shared__ uint32_t s_off[IPCR_SITE_GROUP + 1u];
+    const uint32_t s0 = blockIdx.x * IPCR_SITE_GROUP;
+    if (s0 >= nsites) return;
+    const uint32_t ns = min(IPCR_SITE_GROUP, nsites - s0);
+    if (threadIdx.x < ns) {
+        const ipcr_site_dev s = sites[s0 + threadIdx.x];
+        s_site[threadIdx.x] = s;
+        s_off[threadIdx.x] = s.off;
+        if (threadIdx.x == ns - 1u) s_off[ns] = s.off + s.len;
+    }
+    __syncthreads();
+    const uint32_t o0 = s_off[0], o1 = s_off[ns];
+    for (uint32_t w = (o0 & ~3u) + 4u * threadIdx.x; w < o1; w += 4u * blockDim.x) {
+        const uint32_t first = max(w, o0);
+        uint32_t k = 0, hi = ns; // last site whose output begins at or before `first` (offsets ascend strictly: len >= 1)
+        while (hi - k > 1u) {
+            const uint32_t mid = (k + hi) >> 1;
+            if (s_off[mid] <= first) k = mid; else hi = mid;
+        }
+        uint32_t v = 0, have = 0;
+#pragma unroll
+        for (uint32_t t = 0; t < 4u; ++t) {
+            const uint32_t o = w + t;
+            if (o < o0 || o >= o1) continue;
+            while (o >= s_off[k + 1u]) ++k; // (o < o1 = s_off[ns]: k stays below ns)
+            const ipcr_site_dev s = s_site[k];
+            const uint32_t i = o - s.off;
+            const uint32_t j = s.rc ? (uint32_t)s.len - 1u - i : i;
+            const uint64_t P = s.P + j;
+            uint32_t b = gather_base(planes, rst, P);
+            if (b == (uint32_t)'N' && nruns) {
+                const uint64_t r = exc_first_ending_after(runs, nruns, P);
+                if (r < nruns && runs[r].pos <= P) b = runs[r].byte;
+            }
+            if (s.rc) {
+                const uint32_t c = site_complement(b);
+                if (c) b = c;
+                else atomicMin(bad, ((unsigned long long)(s0 + k) << 16) | ((unsigned long long)j << 8) | b);
+            }
+            v |= b << (8u * t);
+            have |= 1u << t;
+        }
+        if (have == 0xFu) *reinterpret_cast<uint32_t *>(out + w) = v;
+        else
+            for (uint32_t t = 0; t < 4u; ++t)
+                if (have & (1u << t)) out[w + t] = (uint8_t)(v >> (8u * t));
+    }
+}
+
 // ------------------------------------------------------------------------------- probe
 // oligo.BestHit (core/oligo/oligo.go:19-77): one wavefront per amplicon, lanes stride the
 // start offsets; both strands; best = fewest mismatches, then leftmost; '+' wins exact
@@ -1007,6 +1090,14 @@ hipError_t launch_gather(hipStream_t st, const uint32_t *planes, const uint32_t 
                          uint32_t nseg, uint8_t *out, const ipcr_exc_run *runs, uint64_t nruns) {
     if (nseg == 0) return hipSuccess;
     gather_amplicons_kernel<<<dim3(nseg), dim3(256), 0, st>>>(planes, rst, segs, out, runs, nruns);
+    return hipGetLastError();
+}
+
+hipError_t launch_read_sites(hipStream_t st, const uint32_t *planes, const uint32_t *rst, const ipcr_site_dev *sites, uint32_t nsites,
+                             uint8_t *out, const ipcr_exc_run *runs, uint64_t nruns, unsigned long long *bad) {
+    if (nsites == 0) return hipSuccess;
+    read_sites_kernel<<<dim3((nsites + IPCR_SITE_GROUP - 1u) / IPCR_SITE_GROUP), dim3(256), 0, st>>>(planes, rst, sites, nsites, out,
+                                                                                                   runs, nruns, bad);
     return hipGetLastError();
 }
 

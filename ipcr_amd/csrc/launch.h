@@ -45,6 +45,10 @@ hipError_t launch_unpack(hipStream_t st, const uint32_t *planes, const uint32_t 
 // runs: the genome's sorted exception runs (nruns of them) to overwrite the 'N' they decode as; null: tiles only
 hipError_t launch_gather(hipStream_t st, const uint32_t *planes, const uint32_t *rst, const ipcr_amp_seg *segs,
                          uint32_t nseg, uint8_t *out, const ipcr_exc_run *runs = nullptr, uint64_t nruns = 0);
+// short sites in output order (device_types.h: ipcr_site_dev), 256 to a workgroup; *bad (device, preset to all ones) takes the
+// smallest site << 16 | offset << 8 | byte of the bytes a reverse-complemented site could not complement
+hipError_t launch_read_sites(hipStream_t st, const uint32_t *planes, const uint32_t *rst, const ipcr_site_dev *sites, uint32_t nsites,
+                             uint8_t *out, const ipcr_exc_run *runs, uint64_t nruns, unsigned long long *bad);
 hipError_t launch_probe(hipStream_t st, const uint8_t *amps, const uint64_t *amp_off, uint32_t namp,
                         const uint8_t *pmask, const uint8_t *rmask, uint32_t plen, uint32_t max_mm,
                         uint32_t fastpath, ipcr_probe_rec *out,

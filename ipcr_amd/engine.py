@@ -266,16 +266,47 @@ class SimulationScratch:
         return [out[i] for i in range(n)]
 
 
+    def product_sites(self, genome: "Genome") -> List[Tuple[str, str]]:
+        """(FwdSite, RevSite) of every product of the last scan on this scratch over the resident `genome`
+        (ipcr_product_sites: one library call; core/engine/engine.go:177-185): the bases under the left primer, and the
+        reverse complement -- made on the device -- of those under the right one.  Window-local products of a chunked
+        scan are put back into their records by the library."""
+        n = self.num_products()
+        if n == 0:
+            return []
+        offs = (C.c_uint64 * (2 * n + 1))()
+        need = C.c_uint64()
+        cap = 2 * n * _lib.IPCR_MAX_PRIMER_LEN
+        buf = C.create_string_buffer(cap)
+        _lib.check(_lib.lib().ipcr_product_sites(self._h, genome._h, buf, cap, offs, n, C.byref(need)))
+        raw = buf.raw[:need.value].decode("latin-1")
+        return [(raw[offs[2 * i]:offs[2 * i + 1]], raw[offs[2 * i + 1]:offs[2 * i + 2]]) for i in range(n)]
+
+
 def _fill_sites(pr: Product, seq: bytes) -> None:
     """FwdSite / RevSite as core/engine/engine.go:175-183 slices them (NeedSites, pretty text only):
     the target under the left primer, and the reverse complement of the target under the right one."""
+    pr.FwdSite, pr.RevSite = host_sites(seq, pr.Start, pr.End, len(pr.FwdPrimer), len(pr.RevPrimer))
+
+
+def host_sites(seq: bytes, start: int, end: int, flen: int, rlen: int) -> Tuple[str, str]:
+    """(FwdSite, RevSite) of a product [start, end) sliced from the bytes of its record or chunk on the host"""
     from .primer import RevComp
-    flen, rlen = len(pr.FwdPrimer), len(pr.RevPrimer)
-    if pr.Start + flen <= len(seq):
-        pr.FwdSite = seq[pr.Start:pr.Start + flen].decode("latin-1")
-    b = pr.End - rlen
-    if 0 <= b and pr.End <= len(seq):
-        pr.RevSite = RevComp(seq[b:pr.End]).decode("latin-1")   # raises where the reference panics (rc.go:27-34)
+    fwd = rev = ""
+    if start + flen <= len(seq):
+        fwd = seq[start:start + flen].decode("latin-1")
+    b = end - rlen
+    if 0 <= b and end <= len(seq):
+        rev = RevComp(seq[b:end]).decode("latin-1")             # raises where the reference panics (rc.go:27-34)
+    return fwd, rev
+
+
+def _with_sites(cp: CompiledPanel, scratch: SimulationScratch, genome: "Genome", products: List[Product]) -> List[Product]:
+    """NeedSites over a resident genome: FwdSite / RevSite from the device (one call); nothing without the flag"""
+    if cp.Cfg.NeedSites and products:
+        for pr, (f, r) in zip(products, scratch.product_sites(genome)):
+            pr.FwdSite, pr.RevSite = f, r
+    return products
 
 
 def _product(cp: CompiledPanel, p: _lib.Product, seq_ids: Sequence[str]) -> Product:
@@ -360,6 +391,24 @@ class Genome:
             total += (e - s) if s <= e else self.record_len(int(r)) - s + e
         buf = C.create_string_buffer(max(total, 1))
         _lib.check(_lib.lib().ipcr_genome_read_windows(self._h, arr, n, buf, max(total, 0), offs, C.byref(need)))
+        raw = buf.raw
+        return [raw[offs[i]:offs[i + 1]] for i in range(n)]
+
+    def read_sites(self, sites) -> List[bytes]:
+        """Exact bytes of (record, pos, length, revcomp) sites, as loaded (ipcr_genome_read_sites): record[pos:pos+length],
+        reverse-complemented on the device when `revcomp` (core/primer/rc.go:8-24).  One call for all of them."""
+        n = len(sites)
+        arr = (_lib.Site * max(n, 1))()
+        total = 0
+        for i, (r, p, ln, rc) in enumerate(sites):
+            if not 0 <= int(ln) <= 0xFFFF:
+                raise _lib.IpcrError(_lib.ERR_INVALID, f"read_sites: site {i}: length {ln} is not in 1..{_lib.IPCR_MAX_PRIMER_LEN}")
+            arr[i].record, arr[i].pos, arr[i].len, arr[i].revcomp = int(r), int(p), int(ln), 1 if rc else 0
+            total += int(ln)
+        offs = (C.c_uint64 * (n + 1))()
+        need = C.c_uint64()
+        buf = C.create_string_buffer(max(total, 1))
+        _lib.check(_lib.lib().ipcr_genome_read_sites(self._h, arr, n, buf, total, offs, C.byref(need)))
         raw = buf.raw
         return [raw[offs[i]:offs[i + 1]] for i in range(n)]
 
@@ -488,12 +537,15 @@ class Engine:
         return self.SimulateBatch(seqID, seq, SelfPairs(oligos))
 
     # -- resident-genome form of ForEachCompiledProduct: all records in one launch
-    def ScanGenome(self, genome: Genome, cp: CompiledPanel, scratch: SimulationScratch) -> List[Product]:
+    def ScanGenome(self, genome: Genome, cp: CompiledPanel, scratch: SimulationScratch, sites: bool = True) -> List[Product]:
+        """sites=False leaves FwdSite / RevSite empty under NeedSites too: the caller fills them (pipeline.Batch.sites,
+        which knows a fall-back for a genome without exception runs)"""
         _lib.check(_lib.lib().ipcr_scan_genome(cp._h, scratch._h, genome._h, None, None))
-        return scratch.products(genome.ids)
+        prods = scratch.products(genome.ids)
+        return _with_sites(cp, scratch, genome, prods) if sites else prods
 
     def ScanGenomeChunked(self, genome: Genome, cp: CompiledPanel, scratch: SimulationScratch, chunkSize: int,
-                          overlap: int) -> List[Product]:
+                          overlap: int, sites: bool = True) -> List[Product]:
         """The resident genome scanned as the pipeline scans it under --chunk-size (core/fasta/path_ctx.go:83-179 windows,
         one Engine.ForEachCompiledProduct call per window: internal/pipeline/pipeline.go:60-125) -- from ONE sweep of the
         tiles.  Products carry window-local coordinates and the window's ID ('id:start-end', or the record's own ID when
@@ -501,7 +553,8 @@ class Engine:
         _lib.check(_lib.lib().ipcr_scan_genome_chunked(cp._h, scratch._h, genome._h, chunkSize, overlap, None, None))
         ids = genome.ids
         names = [ids[w.record] if w.plain else "%s:%d-%d" % (ids[w.record], w.start, w.end) for w in scratch.chunk_windows()]
-        return scratch.products(names)
+        prods = scratch.products(names)                                  # (sites: as for ScanGenome)
+        return _with_sites(cp, scratch, genome, prods) if sites else prods
 
     def ScanGenomeCount(self, genome: Genome, cp: CompiledPanel, scratch: SimulationScratch) -> int:
         """Same scan + join, products left in the scratch (no Python object per product)."""

@@ -4,7 +4,8 @@ internal/nestedcli/options.go:63-118 and the common flags of `ipcr_amd.cli`.
 Every outer product's amplicon is scanned with the inner panel on the device in one batch (ipcr_amd.nested); the
 best inner product follows internal/visitors/nested.go:35-51.  The data paths are those of `ipcr_amd.pipeline`: NestedProducts
 over a resident genome (whole records or `--chunk-size`), NestedScratchProducts over a streamed chunk.  Output: text (nestedoutput/text.go), jsonl and json (api.NestedProductV1, pkg/api/nested_v1.go);
-`seq` is the outer amplicon's exact bytes, as NestedWriterFactory.NeedSeq() always asks for them.  --pretty is out of scope.
+`seq` is the outer amplicon's exact bytes, as NestedWriterFactory.NeedSeq() always asks for them.  --pretty (text) writes the
+plain alignment block of the OUTER product under its row (nestedoutput/pretty.go:7-9).
 
     python -m ipcr_amd.nested_cli --outer-primers O.tsv --inner-primers I.tsv --output jsonl --sort g.fa
 """
@@ -15,7 +16,7 @@ import json
 import sys
 from typing import Optional, Sequence
 
-from . import nested, pipeline, primer
+from . import nested, pipeline, pretty, primer
 from .cli import Collector, _text, go_json_escape, load_tsv, product_sort_key, validate_chunking
 
 TSV_HEADER_NESTED = ("source_file\tsequence_id\touter_experiment_id\touter_start\touter_end\touter_length\touter_type\t"
@@ -178,7 +179,8 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
     chunk, overlap, warns = validate_chunking(o.circular, o.chunk_size, eff_max, max_primer_len)
     for w in warns:
         print(f"warning: {w}", file=stderr)
-    eng = pipeline.new_engine(o, MinLen=o.min_length, MaxLen=o.max_length, HitCap=o.hit_cap, Circular=o.circular)
+    eng = pipeline.new_engine(o, MinLen=o.min_length, MaxLen=o.max_length, HitCap=o.hit_cap, Circular=o.circular,
+                              NeedSites=pipeline.want_pretty(o))
     cp = eng.CompilePanel(outer_pairs)
     sc = eng.NewSimulationScratch(cp)
     ieng = pipeline.new_engine(o)       # the inner engine (app.go:154-165): linear amplicons, no length bounds, no hit cap
@@ -204,6 +206,8 @@ def run(argv: Optional[Sequence[str]] = None, stdout=None, stderr=None) -> int:
             print(TSV_HEADER_NESTED, file=stdout)
         for path, np, _ in rows:
             print(format_row(path, np), file=stdout)
+            if pipeline.want_pretty(o):
+                pipeline.write_text(stdout, pretty.render_product(np.Product))
     return pipeline.exit_code(o, rows)
 
 

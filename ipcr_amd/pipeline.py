@@ -29,6 +29,7 @@ def add_common_flags(ap: argparse.ArgumentParser, output: dict, chunk_size_help:
     ap.add_argument("--sort", action="store_true")
     ap.add_argument("--output", "-o", default="text", **output)
     ap.add_argument("--no-header", action="store_true")
+    ap.add_argument("--pretty", action="store_true", help="text output: the alignment block under every row")
     ap.add_argument("--no-match-exit-code", type=int, default=0)
     ap.add_argument("--chunk-size", type=int, default=0, help=chunk_size_help)
     ap.add_argument("--dedup-cap", type=int, default=0)
@@ -36,12 +37,37 @@ def add_common_flags(ap: argparse.ArgumentParser, output: dict, chunk_size_help:
     ap.add_argument("fasta", nargs="*")
 
 
+def want_pretty(o) -> bool:
+    """the block is written, and the engine asked for sites, only by the text writer (appcore/writer_factories.go:36-38);
+    every other format accepts the flag and ignores it"""
+    return bool(o.pretty) and o.output == "text"
+
+
 def new_engine(o, **bounds) -> engine.Engine:
-    """the engine of the common flags on --device; `bounds`: MinLen / MaxLen / HitCap / Circular, which the inner engine
-    of ipcr-nested leaves at zero"""
+    """the engine of the common flags on --device; `bounds`: MinLen / MaxLen / HitCap / Circular / NeedSites, which the
+    inner engine of ipcr-nested leaves at zero"""
     _lib.check(_lib.lib().ipcr_set_device(o.device))
+    return engine.New(engine_config(o, **bounds))
+
+
+def engine_config(o, **bounds) -> engine.Config:
     tw = o.terminal_window if o.terminal_window >= 1 else 0            # runutil.EffectiveTerminalWindow
-    return engine.New(engine.Config(MaxMM=o.mismatches, TerminalWindow=tw, SeedLen=o.seed_length, **bounds))
+    return engine.Config(MaxMM=o.mismatches, TerminalWindow=tw, SeedLen=o.seed_length, **bounds)
+
+
+def write_text(stdout, text: str) -> None:
+    """`text` to the driver's stdout handle as UTF-8 (the pretty block holds a non-ASCII glyph): a text handle that cannot
+    encode it and has a byte buffer underneath gets the bytes, every other handle the string"""
+    if not text:
+        return
+    enc = (getattr(stdout, "encoding", None) or "utf-8").lower().replace("-", "").replace("_", "")
+    buf = getattr(stdout, "buffer", None)
+    if enc != "utf8" and buf is not None:
+        stdout.flush()
+        buf.write(text.encode("utf-8"))
+        buf.flush()
+    else:
+        stdout.write(text)
 
 
 def exit_code(o, rows) -> int:
@@ -75,11 +101,30 @@ class Batch:
         except _lib.IpcrError as e:
             if e.status != _lib.ERR_UNSUPPORTED:
                 raise
-        wanted, recs = {r for r, _, _ in self.windows}, {}              # (the genome keeps no exception runs:
-        for i, rec in enumerate(fasta.StreamChunks(self.path, 0, 0)):   # whole records streamed on the host)
+        recs = self._host_records()
+        return [_cut(recs[r], a, b) for r, a, b in self.windows]
+
+    def _host_records(self) -> dict:
+        """the genome keeps no exception runs: the records the products lie in, streamed whole on the host"""
+        wanted, recs = {r for r, _, _ in self.windows}, {}
+        for i, rec in enumerate(fasta.StreamChunks(self.path, 0, 0)):
             if i in wanted:
                 recs[i] = rec.Seq
-        return [_cut(recs[r], a, b) for r, a, b in self.windows]
+        return recs
+
+    def sites(self) -> List[tuple]:
+        """(FwdSite, RevSite) of every product (core/engine/engine.go:177-185): read and reverse-complemented on the
+        device for a resident genome (one call), sliced from the chunk in hand otherwise"""
+        if self.genome is None:
+            return [engine.host_sites(self.chunk, p.Start, p.End, len(p.FwdPrimer), len(p.RevPrimer)) for p in self.products]
+        try:
+            return self.sc.product_sites(self.genome)
+        except _lib.IpcrError as e:
+            if e.status != _lib.ERR_UNSUPPORTED:
+                raise
+        recs = self._host_records()
+        return [engine.host_sites(recs[r], a, b, len(p.FwdPrimer), len(p.RevPrimer))
+                for p, (r, a, b) in zip(self.products, self.windows)]
 
     def probe_hits(self, probe: str, max_mm: int):
         """ipcr-probe keeps --chunk-size (internal/probeapp/app.go:108): every product is annotated from its own
@@ -112,6 +157,9 @@ def scan_files(paths: Sequence[str], eng: engine.Engine, cp: engine.CompiledPane
 
     def keep(path: str, batch: Batch) -> None:
         if batch.products:
+            if cp.Cfg.NeedSites and batch.genome is not None:           # (a streamed chunk's products have theirs)
+                for p, (fwd, rev) in zip(batch.products, batch.sites()):
+                    p.FwdSite, p.RevSite = fwd, rev
             for p, *rest in visit(batch):                               # (raises before the first row is kept)
                 if collector.add(path, p) is not None:
                     rows.append((path, p, *rest))
@@ -124,7 +172,8 @@ def scan_files(paths: Sequence[str], eng: engine.Engine, cp: engine.CompiledPane
                 try:
                     g.add_fasta(path)
                     # whole records, or --chunk-size: one sweep, every rolling window joined on its own
-                    prods = eng.ScanGenomeChunked(g, cp, sc, chunk, overlap) if chunk else eng.ScanGenome(g, cp, sc)
+                    prods = eng.ScanGenomeChunked(g, cp, sc, chunk, overlap, sites=False) if chunk else \
+                        eng.ScanGenome(g, cp, sc, sites=False)
                     keep(path, Batch(prods, sc, g, sc.chunk_windows() if chunk else None, path=path))
                     continue
                 except _lib.IpcrError as e:                             # (a capped scan that ran in segments: stream the chunks)
