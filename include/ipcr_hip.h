@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define IPCR_ABI_VERSION 5
+#define IPCR_ABI_VERSION 6
 #define IPCR_MAX_PRIMER_LEN 128 /* longest primer/probe the device path accepts */
 #define IPCR_MAX_MM 16          /* largest --mismatches the device path accepts */
 
@@ -491,6 +491,48 @@ ipcr_status ipcr_nested_products(const ipcr_scratch *outer, const ipcr_genome *g
  * IPCR_ERR_DEVICE for a host-only scratch.  An empty chunk scan returns IPCR_OK and writes nothing. */
 ipcr_status ipcr_nested_scratch_products(const ipcr_scratch *outer, const ipcr_panel *inner, ipcr_scratch *inner_scratch,
                                          ipcr_nested_hit *out, int64_t n_out);
+
+
+/* ---- ipcr-thermo, --thermo-model legacy-heuristic: thermovisitors.Score.visitLegacyHeuristic -- internal/thermovisitors/score.go:1522-1552 ----
+ * Score = -(penalty of the left end + penalty of the right end).  Left end: the product's left primer (a revcomp product's is
+ * the pair's reverse primer, engine.go:326-331) against the base-by-base complement of the first |primer| bases of the
+ * amplicon; right end: its right primer against the complement of the LAST |primer| bases, complemented base by base and not
+ * reversed (score.go:1539-1547, restated as it is).  An end adds nothing when its primer is not pure ACGT or the amplicon is
+ * shorter than the primer; two perfect ends score -0.0.  The penalty of an end is ipcr_thermo_legacy_penalty below; --allow-indel
+ * cannot change it (a primer and a window of equal length: the gap state of the reference's DP never reaches its last cell).
+ * The NN models (nn-duplex-v1, nn-structure-v1) and --single-stranded are not built.
+ *
+ * ipcr_thermo_legacy_products: every product of the last scan on `s` over the resident genome `g`, scored on the device: one
+ * kernel reads the two windows of a product from the tiles and writes one double (out[i] <-> product i); one launch per 2^21
+ * products.  A window base is A/C/G/T where the tiles hold an upper-case A/C/G/T and N otherwise, so the call needs no
+ * exception runs (it works on a genome that dropped them) and a raw record's lower-case base reads as N, as the reference's
+ * compBase reads it.  After ipcr_scan_genome_chunked the products' window-local coordinates are put back into their records
+ * first.  denom[2 p] / denom[2 p + 1]: the denominator D (cal/K/mol) of pair p's forward / reverse primer -- a property of the
+ * primer (--denom auto: score.go:465-492, computed by the caller); n_denom = 0 (denom may be NULL): 200.0 for every primer
+ * (--denom fixed), else n_denom must be twice the panel's pair count.  D <= 0 makes every mismatch cost 4.0 (mismatch.go:184-189).
+ * The device result equals ipcr_thermo_legacy_penalty's bit for bit (one implementation, no fused multiply-add on either side).
+ * Every index is checked on the host before anything is launched: IPCR_ERR_INVALID when n_products differs from the scratch's
+ * product count, n_denom is neither 0 nor twice the pair count, a product's pair or record does not exist, a window leaves its
+ * record, the scratch and the genome live on different devices, or the last scan was an ipcr_scan_chunk.  n_products == 0 is
+ * IPCR_OK.  Safe from several threads at once, next to scans on other scratches.
+ * ipcr_thermo_legacy_scratch_products: the same for the products of the LAST ipcr_scan_chunk on `s`, read from the tiles that
+ * call packed (chunk-local coordinates); IPCR_ERR_INVALID when the last scan was not an ipcr_scan_chunk. */
+ipcr_status ipcr_thermo_legacy_products(const ipcr_scratch *s, const ipcr_genome *g, const double *denom, int64_t n_denom,
+                                        double *out, int64_t n_products);
+ipcr_status ipcr_thermo_legacy_scratch_products(const ipcr_scratch *s, const double *denom, int64_t n_denom, double *out,
+                                                int64_t n_products);
+/* host only, no device: the penalty of one end -- alignPenaltyC_contextualD_ss (score.go:363-458), single-stranded mode off --
+ * for a primer (5'->3') on a target given 3'->5' of the SAME length n: the sum, left to right over the positions i whose pair is
+ * not Watson-Crick, of mm(i) * w(i), clamped at 0; w(i) = 2.0 for i >= n - 3, else 1.5 for i < 3, else 1.0; mm(i) =
+ * ddG * 1000 / denom for denom > 0, else 4.0; ddG = ipcr_thermo_mismatch_ddg with the flanks taken from the two strings (N
+ * outside them).  Case is folded; a primer with a byte outside ACGT or a target with one outside ACGTN scores 0.0, as an
+ * empty string does.  IPCR_ERR_INVALID when the lengths differ (the model never compares such a pair). */
+ipcr_status ipcr_thermo_legacy_penalty(const char *primer5to3, const char *target3to5, double denom, double *out);
+/* thermo.LookupDeltaG -- core/thermo/mismatch.go:108-179, kcal/mol: the exact triplet value when all six bytes are ACGT and
+ * both flanks are Watson-Crick pairs (192 contexts), else the pair-family value by (p, t) for t in ACGT, else (t == 'N') the
+ * context heuristic: 1.0, less 0.05 when the four flanks hold at least two more G/C than A/T.  Upper case only, as the
+ * reference; IPCR_ERR_INVALID where its look-up returns ok == false (p outside ACGT, t outside ACGTN). */
+ipcr_status ipcr_thermo_mismatch_ddg(char p5, char p, char p3, char t5, char t, char t3, double *out);
 
 #ifdef __cplusplus
 }

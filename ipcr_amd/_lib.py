@@ -180,6 +180,10 @@ SYMBOLS = {
     "ipcr_nested_windows": (C.c_int, [C.c_void_p, C.POINTER(Window), C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(NestedHit)]),
     "ipcr_nested_products": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NestedHit), C.c_int64]),
     "ipcr_nested_scratch_products": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NestedHit), C.c_int64]),
+    "ipcr_thermo_legacy_products": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.c_int64]),
+    "ipcr_thermo_legacy_scratch_products": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.c_int64]),
+    "ipcr_thermo_legacy_penalty": (C.c_int, [C.c_char_p, C.c_char_p, C.c_double, C.POINTER(C.c_double)]),
+    "ipcr_thermo_mismatch_ddg": (C.c_int, [C.c_char, C.c_char, C.c_char, C.c_char, C.c_char, C.c_char, C.POINTER(C.c_double)]),
 }
 
 _lib = None

@@ -56,6 +56,21 @@ struct ipcr_site_dev {
     uint16_t len, rc;
 };
 
+// legacy-heuristic thermo score (thermo_kernels.hip).  A primer of the panel as codes (thermo_legacy.h: A 0 C 1 G 2 T 3) with
+// its denominator D; len == 0: the primer is not pure ACGT and its end adds nothing.  Entry 2 p is pair p's forward primer,
+// 2 p + 1 its reverse primer.
+struct ipcr_thermo_primer {
+    double denom;
+    uint32_t len, reserved;
+    uint8_t code[128];
+};
+// one end of a product: the n bases from padded position P under primer `primer`; n == 0: the end adds nothing (no pure
+// ACGT primer, or a product shorter than it).  Ends 2 i and 2 i + 1 are the left and the right end of product i.
+struct ipcr_thermo_end {
+    uint64_t P;
+    uint32_t primer, n;
+};
+
 struct ipcr_probe_rec { // layout-identical to ipcr_probe_hit
     int32_t found, strand, pos, mm;
 };

@@ -44,6 +44,7 @@
 #include "fasta_hostpack.h"
 #include "jit.h"
 #include "launch.h"
+#include "thermo_legacy.h"
 #include "tile_layout.h"
 
 using ipcr::PackPool;          // cpu_pool.h: the process's pool of pack threads
@@ -1795,6 +1796,12 @@ struct ReadCtx {
     // kernel reports a byte without a complement through
     ipcr_site_dev *d_sites = nullptr, *h_sites = nullptr; // h_sites pinned
     unsigned long long *d_bad = nullptr, *h_bad = nullptr; // h_bad pinned
+    // thermo_run (grown by its calls on this context, never shrunk): the ends of one piece, and the panel's primer table;
+    // the scores of a piece land in d_out
+    ipcr_thermo_end *d_ends = nullptr, *h_ends = nullptr; // h_ends pinned
+    uint64_t ends_cap = 0;                                // in products (two ends each)
+    ipcr_thermo_primer *d_primers = nullptr;
+    uint64_t primers_cap = 0;
 };
 std::mutex g_read_mu;
 std::vector<ReadCtx *> g_read_free;
@@ -4248,6 +4255,136 @@ ipcr_status ipcr_product_sites(const ipcr_scratch *s, const ipcr_genome *g, uint
         sites[2 * i + 1] = ipcr_site{w[i].end - (int64_t)right, w[i].record, (uint16_t)right, 1};
     }
     return read_sites("ipcr_product_sites", const_cast<ipcr_genome *>(g), sites.data(), (int64_t)(2 * n), out, cap, offsets, needed);
+}
+
+// ------------------------------------------------------------------------------ thermo: legacy-heuristic score
+
+// The one body of ipcr_thermo_legacy_products / ipcr_thermo_legacy_scratch_products (`what` names the caller in messages):
+// Score of every product of the last scan on `s` (internal/thermovisitors/score.go:1522-1552), the two primer-length windows
+// read from the tiles of `g` -- the resident genome, or the scratch's private chunk genome -- on the device.  Everything is
+// checked here, before anything is launched: the kernel trusts its descriptors.
+static ipcr_status thermo_run(const char *what, const ipcr_scratch *s, const ipcr_genome *cg, bool in_windows, const double *denom,
+                              int64_t n_denom, double *out, int64_t n_products) {
+    const ipcr_panel *p = s->panel;
+    const size_t n = s->products.size(), npairs = p->fwd.size();
+    if ((int64_t)n != n_products) return fail(IPCR_ERR_INVALID, "%s: n_products (%lld) != products of the last scan (%zu)", what, (long long)n_products, n);
+    if (n_denom != 0 && (n_denom != (int64_t)(2 * npairs) || !denom))
+        return fail(IPCR_ERR_INVALID, "%s: n_denom (%lld) must be 0 or twice the panel's pair count (%zu), with a table", what, (long long)n_denom, npairs);
+    if (n && !out) return fail(IPCR_ERR_INVALID, "%s: null output", what);
+    { const ipcr_status ds = same_device(s, cg); if (ds != IPCR_OK) return ds; }
+    if (n == 0) return IPCR_OK;
+    ipcr_genome *g = const_cast<ipcr_genome *>(cg);
+    // the primers: entry 2 p = pair p's forward primer, 2 p + 1 its reverse primer; a primer that is not pure ACGT has
+    // length 0 here and its end adds nothing (toUpperACGT, score.go:239-251: panel primers are upper case already)
+    std::vector<ipcr_thermo_primer> prim(2 * npairs);
+    for (size_t k = 0; k < 2 * npairs; ++k) {
+        const std::string &seq = (k & 1) ? p->rev[k >> 1] : p->fwd[k >> 1];
+        ipcr_thermo_primer &t = prim[k];
+        memset(&t, 0, sizeof t);
+        t.denom = n_denom ? denom[k] : IPCR_THERMO_FIXED_DENOM;
+        bool pure = !seq.empty() && seq.size() <= IPCR_MAX_PRIMER_LEN;
+        for (size_t j = 0; j < seq.size() && pure; ++j) {
+            const uint32_t c = ipcr_thermo_code((uint8_t)seq[j]);
+            if (c >= 4u) pure = false; else t.code[j] = (uint8_t)c;
+        }
+        t.len = pure ? (uint32_t)seq.size() : 0u;
+    }
+    // the ends: left = the first |left primer| bases of the amplicon, right = its last |right primer| bases; a revcomp
+    // product's left primer is the pair's reverse primer (engine.go:326-331).  An end is skipped when the amplicon is shorter
+    // than its primer (score.go:1530, :1540).  A primer never spans the origin, so both windows lie whole in the record, also
+    // for a wrap-around product.
+    const std::vector<ipcr_window> w = outer_windows(s, in_windows);
+    std::vector<ipcr_thermo_end> ends(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const ipcr_product &pr = s->products[i];
+        if (pr.pair < 0 || (size_t)pr.pair >= npairs) return fail(IPCR_ERR_INVALID, "%s: product %zu: no pair %d", what, i, pr.pair);
+        if (w[i].record < 0 || (size_t)w[i].record >= g->rec_len.size()) return fail(IPCR_ERR_INVALID, "%s: product %zu: no record %d", what, i, w[i].record);
+        const int64_t L = (int64_t)g->rec_len[(size_t)w[i].record], a = w[i].start, b = w[i].end;
+        if (a < 0 || b < 0 || a > L || b > L)
+            return fail(IPCR_ERR_INVALID, "%s: product %zu [%lld, %lld) outside its record of %lld bases", what, i, (long long)a, (long long)b, (long long)L);
+        const int64_t amp = a <= b ? b - a : (L - a) + b;
+        const uint64_t R = g->rec_start[(size_t)w[i].record];
+        const uint32_t left = 2u * (uint32_t)pr.pair + (pr.type == 0 ? 0u : 1u), right = left ^ 1u;
+        const int64_t ln = (int64_t)prim[left].len, rn = (int64_t)prim[right].len;
+        ipcr_thermo_end &el = ends[2 * i], &er = ends[2 * i + 1];
+        el = ipcr_thermo_end{0, left, 0};
+        er = ipcr_thermo_end{0, right, 0};
+        if (ln && amp >= ln) {
+            if (ln > L - a) return fail(IPCR_ERR_INVALID, "%s: product %zu: the %lld bases under its left primer at %lld leave its record of %lld bases", what, i, (long long)ln, (long long)a, (long long)L);
+            el.P = R + (uint64_t)a;
+            el.n = (uint32_t)ln;
+        }
+        if (rn && amp >= rn) {
+            if (rn > b) return fail(IPCR_ERR_INVALID, "%s: product %zu: the %lld bases under its right primer end at %lld, before its record begins", what, i, (long long)rn, (long long)b);
+            er.P = R + (uint64_t)(b - rn);
+            er.n = (uint32_t)rn;
+        }
+    }
+    DeviceGuard dg(g->device);
+    {   // padding and packing must be complete: waits on the host for the genome's own stream (a chunk genome's is its scratch's)
+        std::lock_guard<std::mutex> lk(g->read_mu);
+        const ipcr_status st = genome_finalize(g);
+        if (st != IPCR_OK) return st;
+    }
+    uint64_t piece = READ_PIECE_SITES; // products per launch
+    if (const char *e = getenv("IPCR_TEST_THERMO_PIECE"))
+        if (*e) piece = std::min<uint64_t>(piece, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
+    piece = std::min<uint64_t>(piece, n);
+    ReadCtx *c = nullptr;
+    ipcr_status st = read_ctx_acquire(g->device, &c);
+    if (st != IPCR_OK) return st;
+    hipError_t e = hipSuccess;
+    if (c->ends_cap < piece) {
+        if (c->d_ends) (void)hipFree(c->d_ends);
+        if (c->h_ends) (void)hipHostFree(c->h_ends);
+        c->d_ends = c->h_ends = nullptr;
+        c->ends_cap = 0;
+        const uint64_t cap = std::min<uint64_t>(READ_PIECE_SITES, std::max<uint64_t>(piece + (piece >> 1), 4096));
+        e = hipMalloc((void **)&c->d_ends, cap * 2 * sizeof(ipcr_thermo_end));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_ends, cap * 2 * sizeof(ipcr_thermo_end), hipHostMallocDefault);
+        if (e == hipSuccess) c->ends_cap = cap;
+    }
+    if (e == hipSuccess && c->primers_cap < prim.size()) {
+        if (c->d_primers) (void)hipFree(c->d_primers);
+        c->d_primers = nullptr;
+        c->primers_cap = 0;
+        const uint64_t cap = std::max<uint64_t>(prim.size() * 2, 64);
+        e = hipMalloc((void **)&c->d_primers, cap * sizeof(ipcr_thermo_primer));
+        if (e == hipSuccess) c->primers_cap = cap;
+    }
+    static_assert(READ_PIECE_SITES * sizeof(double) <= READ_PIECE_BYTES, "a piece's scores fit the context's output buffer");
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_primers, prim.data(), prim.size() * sizeof(ipcr_thermo_primer), hipMemcpyHostToDevice, c->st);
+    for (size_t i0 = 0; i0 < n && e == hipSuccess; i0 += piece) {
+        const size_t m = std::min<size_t>(piece, n - i0);
+        memcpy(c->h_ends, ends.data() + 2 * i0, 2 * m * sizeof(ipcr_thermo_end));
+        e = hipMemcpyAsync(c->d_ends, c->h_ends, 2 * m * sizeof(ipcr_thermo_end), hipMemcpyHostToDevice, c->st);
+        if (e == hipSuccess) e = ipcr::launch_thermo_legacy(c->st, g->planes, c->d_ends, (uint32_t)m, c->d_primers, (uint32_t)prim.size(), reinterpret_cast<double *>(c->d_out));
+        if (e == hipSuccess) e = hipMemcpyAsync(out + i0, c->d_out, m * sizeof(double), hipMemcpyDeviceToHost, c->st);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->st); // (h_ends, d_out -- and `prim` -- are free for reuse after it)
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(c->st);
+    read_ctx_release(c);
+    if (e != hipSuccess) return fail(IPCR_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+    return IPCR_OK;
+}
+
+ipcr_status ipcr_thermo_legacy_products(const ipcr_scratch *s, const ipcr_genome *g, const double *denom, int64_t n_denom, double *out,
+                                        int64_t n_products) {
+    if (!s || !g) return fail(IPCR_ERR_INVALID, "ipcr_thermo_legacy_products: null argument");
+    if (!s->products.empty() && s->last_was_chunk)
+        return fail(IPCR_ERR_INVALID, "ipcr_thermo_legacy_products: the last scan was an ipcr_scan_chunk: ipcr_thermo_legacy_scratch_products scores its products");
+    return thermo_run("ipcr_thermo_legacy_products", s, g, s->products_in_windows, denom, n_denom, out, n_products);
+}
+
+ipcr_status ipcr_thermo_legacy_scratch_products(const ipcr_scratch *s, const double *denom, int64_t n_denom, double *out, int64_t n_products) {
+    if (!s) return fail(IPCR_ERR_INVALID, "ipcr_thermo_legacy_scratch_products: null argument");
+    if (!s->stream) return fail(IPCR_ERR_DEVICE, "host-only scratch: the thermo score has no CPU fallback");
+    if (!s->last_was_chunk) return fail(IPCR_ERR_INVALID, "ipcr_thermo_legacy_scratch_products: the scratch's last scan was not an ipcr_scan_chunk");
+    if (!s->chunk) { // (an empty chunk, or an empty panel's chunk scan, which packs nothing)
+        if (s->products.empty() && n_products == 0) return IPCR_OK;
+        return fail(IPCR_ERR_INVALID, "ipcr_thermo_legacy_scratch_products: the scratch holds no chunk");
+    }
+    return thermo_run("ipcr_thermo_legacy_scratch_products", s, s->chunk, false, denom, n_denom, out, n_products);
 }
 
 // ipcr-nested on a worker: the products of the outer scratch's last ipcr_scan_chunk, their amplicons read from the tiles

@@ -58,6 +58,10 @@ hipError_t launch_probe_tiles(hipStream_t st, const uint32_t *planes, const uint
                               const uint8_t *pmask, const uint8_t *rmask, uint32_t plen, uint32_t max_mm, uint32_t fastpath,
                               ipcr_probe_rec *out, uint32_t tag);
 inline uint64_t launch_probe_tiles_max() { return 16384u; } // IPCR_PROBE_LDS_BYTES (kernels.hip)
+// legacy-heuristic thermo score (thermo_kernels.hip): ends 2 i, 2 i + 1 = the two ends of product i -> out[i] = Score; the
+// caller has checked every window against its record and every primer index against the table
+hipError_t launch_thermo_legacy(hipStream_t st, const uint32_t *planes, const ipcr_thermo_end *ends, uint32_t nproducts,
+                                const ipcr_thermo_primer *primers, uint32_t nprimers, double *out);
 // header lines ('>' at a line start .. its line end) of a raw FASTA slab, unordered; *count may exceed cap
 hipError_t launch_fasta_find_headers(hipStream_t st, const uint8_t *raw, uint64_t n, uint32_t at_line_start, ipcr_fasta_range *list,
                                      uint32_t cap, uint32_t *count);

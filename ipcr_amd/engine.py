@@ -54,6 +54,7 @@ class Product:
     FwdSite: str = ""
     RevSite: str = ""
     Record: int = 0
+    Score: float = 0.0          # ipcr-thermo only (product.go: Score); every other driver leaves it 0
 
     def sig(self):
         """core/engine/approx_seed_oracle_test.go:12-41 signature (minus SequenceID)."""
@@ -281,6 +282,23 @@ class SimulationScratch:
         _lib.check(_lib.lib().ipcr_product_sites(self._h, genome._h, buf, cap, offs, n, C.byref(need)))
         raw = buf.raw[:need.value].decode("latin-1")
         return [(raw[offs[2 * i]:offs[2 * i + 1]], raw[offs[2 * i + 1]:offs[2 * i + 2]]) for i in range(n)]
+
+
+    def thermo_scores(self, genome: Optional["Genome"] = None, denoms: Optional[Sequence[float]] = None) -> List[float]:
+        """Score of every product of the last scan on this scratch under `--thermo-model legacy-heuristic`
+        (internal/thermovisitors/score.go:1522-1552), computed on the device from the tiles: the resident `genome` the scan
+        ran over (ipcr_thermo_legacy_products; window-local coordinates are put back by the library), or -- without one --
+        the chunk of the last ipcr_scan_chunk (ipcr_thermo_legacy_scratch_products).  `denoms`: D of pair p's forward /
+        reverse primer at 2 p / 2 p + 1 (thermo.panel_denoms); None: 200.0 everywhere (--denom fixed)."""
+        n = self.num_products()
+        out = (C.c_double * max(n, 1))()
+        nd = 0 if denoms is None else len(denoms)
+        d = (C.c_double * max(nd, 1))(*(denoms or ())) if nd else None
+        if genome is None:
+            _lib.check(_lib.lib().ipcr_thermo_legacy_scratch_products(self._h, d, nd, out, n))
+        else:
+            _lib.check(_lib.lib().ipcr_thermo_legacy_products(self._h, genome._h, d, nd, out, n))
+        return out[:n]
 
 
 def _fill_sites(pr: Product, seq: bytes) -> None:

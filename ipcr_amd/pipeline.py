@@ -126,6 +126,12 @@ class Batch:
         return [engine.host_sites(recs[r], a, b, len(p.FwdPrimer), len(p.RevPrimer))
                 for p, (r, a, b) in zip(self.products, self.windows)]
 
+    def thermo_scores(self, denoms=None) -> List[float]:
+        """the legacy-heuristic Score of every product (internal/thermovisitors/score.go:1522-1552), computed on the
+        device from the tiles the products were found in: the resident genome, or the chunk the scratch holds.  `denoms`:
+        thermo.panel_denoms (--denom auto), None for 200.0."""
+        return self.sc.thermo_scores(self.genome, denoms)
+
     def probe_hits(self, probe: str, max_mm: int):
         """ipcr-probe keeps --chunk-size (internal/probeapp/app.go:108): every product is annotated from its own
         amplicon, rescanned from the tiles it was found in (pipeline.go:80-89 slices Product.Seq chunk-locally too)"""

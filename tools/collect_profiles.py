@@ -231,6 +231,12 @@ def readme_text():
                            _num(j["median_nested_products_ms"]), _num(j["median_ipcr_nested_products_call_ms"]), _num(r0["inner_filter_ms"])))
                 if j.get("cli"):
                     row += "; CLI wall (s): " + ", ".join("%s %s" % (k, _num(v["median_wall_s"])) for k, v in j["cli"].items())
+            elif f.endswith(".json") and "_thermo_probe" in f:  # tools/thermo_probe.py
+                j = json.load(open(path))
+                row = ("`tools/thermo_probe.py`: legacy-heuristic Score of %d products, median call of %d alternating children (ms): "
+                       "device (`ipcr_thermo_legacy_products`) %s, host route (`ipcr_product_sites` + `ipcr_thermo_legacy_penalty` per end) %s; "
+                       "bitwise equal: %s" % (j["products"], j["rounds"], _num(j["call_s_median"]["device"] * 1e3),
+                                              _num(j["call_s_median"]["host"] * 1e3), j["bitwise_equal"]))
             elif f.endswith(".json") and "_headline_ab" in f:  # alternating bench runs against the parent build
                 j = json.load(open(path))
                 row = "alternating `%s` runs, C2 Gbases/s: %s" % (j["cmd"], ", ".join("%s %s" % (k, " / ".join(_num(v) for v in vs)) for k, vs in j["headline"].items()))
@@ -240,6 +246,12 @@ def readme_text():
                 row = "`rocprofv3 --kernel-trace --stats`: " + "; ".join("`%s` %s calls, average %s us" % (
                     name, rows[name]["Calls"], _num(float(rows[name]["AverageNs"]) / 1e3))
                     for name in ("gather_amplicons_kernel", "pack_batch_kernel", "ipcr_filter", "verify_kernel") if name in rows)
+            if row is None and f.endswith("_stats.csv") and "_thermo" in f:  # the thermo probe's device child under rocprofv3 --stats
+                with open(path, newline="") as fh:
+                    rows = {r.get("Name", "").split("(")[0].replace("void ", ""): r for r in csv.DictReader(fh)}
+                row = "`rocprofv3 --kernel-trace --stats`: " + "; ".join("`%s` %s calls, average %s us" % (
+                    name, rows[name]["Calls"], _num(float(rows[name]["AverageNs"]) / 1e3))
+                    for name in ("thermo_legacy_kernel", "read_sites_kernel") if name in rows)
             if row is None and f.endswith("_stats.csv") and "_read_windows" in f:  # the probe under rocprofv3 --stats
                 with open(path, newline="") as fh:
                     rows = {r.get("Name", "").split("(")[0]: r for r in csv.DictReader(fh)}
