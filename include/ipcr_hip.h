@@ -100,7 +100,13 @@ typedef struct {
 /* per-scan measurements, filled by the last ipcr_scan_* call on a scratch */
 typedef struct {
     double pack_ms;       /* ASCII -> tile pack kernel (0 when the genome was already resident) */
-    double filter_ms;     /* dominant kernel: bit-sliced k-mismatch filter over the tiles (HIP events) */
+    double filter_ms;     /* dominant kernel: bit-sliced k-mismatch filter over the tiles (HIP events): the launch's own start -> stop
+                             time.  A scan chained on the OTHER lane than its predecessor (ipcr_scratch_chain_after, two lanes) overlaps
+                             it, so its own time would count the shared stretch twice; it reports the EXCLUSIVE time instead: own end
+                             - max(own start, end of the sweep of the chain that ended last before it) = the time by which this
+                             sweep extended the device's busy period (0 if it ended under its predecessor).  Over a window of
+                             chained passes these sum to the device's busy time: throughput figures derived from it include the
+                             boundary between sweeps.  A repeated attempt (buffer regrowth) reports its own time. */
     double verify_ms;     /* stand-alone verify kernel (0 when the specialised filter verified its survivors itself) */
     double total_ms;      /* host wall time of the call */
     uint64_t bases;       /* genome bases scanned */
@@ -326,11 +332,16 @@ ipcr_status ipcr_scratch_chunk_windows(const ipcr_scratch *s, const ipcr_chunk_w
  * *n = how many there are (out may be null or shorter: the first `cap` are written) */
 ipcr_status ipcr_chunk_windows(uint64_t len, int64_t chunk_size, int64_t overlap, ipcr_chunk_window *out, int64_t cap, int64_t *n);
 
-/* order two pipelined scans on the device: the next scan begun on `s` runs its filter sweep
- * directly after the filter sweep of the scan most recently begun on `prev` (the two sweeps share
- * one in-order stream, so they never compete for HBM); prev's verify kernel, read-back and
- * host-side join overlap it.  Call after prev's begin() and before s's begin(); scratches of a
- * chain should be destroyed only after their scans have ended. */
+/* order two pipelined scans on the device: the next scan begun on `s` follows the scan most recently begun on
+ * `prev`; prev's read-back and host-side join overlap it.  Call after prev's begin() and before s's begin();
+ * scratches of a chain should be destroyed only after their scans have ended.
+ * IPCR_CHAIN_LANES (read at every call; default 2):
+ *   2  the scans of a chain alternate between TWO in-order streams (the streams of the chain's first two scratches):
+ *      `s` runs on the one `prev` did not use, with no dependency on prev's sweep -- scratches share nothing but the
+ *      read-only genome -- so its waves fill the slots prev's last round of waves leaves empty and the time between
+ *      prev's end and the next dispatch.  Scan i+2 runs behind scan i.  stats.filter_ms of such a scan is its
+ *      exclusive time (ipcr_scan_stats).
+ *   1  ONE in-order stream for the whole chain: a sweep starts when the one before it has ended. */
 ipcr_status ipcr_scratch_chain_after(ipcr_scratch *s, const ipcr_scratch *prev);
 ipcr_status ipcr_scan_genome_end(const ipcr_panel *p, ipcr_scratch *s, const ipcr_genome *g,
                                  ipcr_emit_fn emit, void *user);

@@ -2056,10 +2056,13 @@ struct ipcr_scratch {
     unsigned long long *d_counts = nullptr; // set 0; set 1 = d_counts + 4
     void *d_hitbuf = nullptr;
     uint32_t cset = 0;
-    // pipelined scans (ipcr_scratch_chain_after): the scans of a chain of scratches are enqueued on ONE
-    // in-order stream (the "lane" = the stream of the chain's first scratch), so scan i+1's sweep starts
-    // the moment scan i's kernels and read-back are done, with no cross-stream dependency (tens of
-    // microseconds each on this runtime) in front of the bandwidth-bound kernel
+    // pipelined scans (ipcr_scratch_chain_after): the scans of a chain of scratches are enqueued on in-order
+    // streams ("lanes") with no cross-stream dependency (tens of microseconds each on this runtime) in front
+    // of the bandwidth-bound kernel.  IPCR_CHAIN_LANES=1: ONE lane (the stream of the chain's first scratch),
+    // scan i+1's sweep starts the moment scan i's kernels and read-back are done.  IPCR_CHAIN_LANES=2 (default):
+    // TWO lanes (the streams of the chain's first two scratches) in alternation, so scan i+1 shares nothing with
+    // scan i -- not even the stream -- and its waves fill the slots scan i's last round leaves empty and the
+    // time between scan i's end-of-kernel release and the next dispatch.  Scan i+2 follows scan i on its lane.
     struct Lane {
         hipStream_t s = nullptr;
         ~Lane() { if (s) (void)hipStreamDestroy(s); }
@@ -2067,6 +2070,22 @@ struct ipcr_scratch {
     std::shared_ptr<Lane> own_lane;   // holds `stream`
     std::shared_ptr<Lane> lane_next;  // lane of the next scan (null: own)
     std::shared_ptr<Lane> lane_used;  // lane the last scan ran on
+    std::shared_ptr<Lane> lane_other_next; // the chain's other lane, for the next scan (null: unchained or a one-lane chain)
+    std::shared_ptr<Lane> lane_other;      // ... as of the last scan: the lane a scan chained after it takes
+    // start / stop events of one sweep.  ev[0] / ev[1] are the handles of the last launch's pair; a scan chained
+    // after it on the other lane keeps the pair alive until it has been collected (its exclusive time is measured
+    // against this sweep's end), whatever this scratch launches or whether it still exists by then.
+    struct SweepEv {
+        hipEvent_t start = nullptr, stop = nullptr;
+        std::shared_ptr<SweepEv> frontier; // set when collected: the sweep of the chain that ended last so far (null: this one)
+        ~SweepEv() {
+            if (start) (void)hipEventDestroy(start);
+            if (stop) (void)hipEventDestroy(stop);
+        }
+    };
+    std::vector<std::shared_ptr<SweepEv>> sweep_evs; // every pair this scratch has made; one nobody else holds is used again
+    std::shared_ptr<SweepEv> sweep_ev;               // the last launch's
+    std::shared_ptr<SweepEv> pred_next;              // the sweep the next scan follows on the other lane (ipcr_scratch_chain_after)
     hipEvent_t ev_done = nullptr;     // recorded behind a scan's read-back when it runs on a shared lane
     hipStream_t cstream = nullptr;    // fetches the hit records of a published scan (never waits behind a sweep)
     struct Pending { // a scan enqueued by scan_enqueue and not yet collected
@@ -2077,6 +2096,7 @@ struct ipcr_scratch {
         bool on_lane = false;  // wait for ev_done (false: a follow-up on the private stream, wait for the stream)
         bool published = false; // the filter's last wave writes counters + sequence word to pinned memory: poll
         bool times_pending = false;
+        std::shared_ptr<SweepEv> pred; // the sweep in front of this one on the chain's other lane (null: none, filter_ms is the launch's own time)
         uint32_t nrec = 0, check_rst = 0, cset_used = 0;
         uint64_t nblocks = 0, pre = 0;
         uint64_t block0 = 0;   // the launch sweeps blocks [block0, block0 + nblocks): the whole genome unless ...
@@ -2450,10 +2470,36 @@ ipcr_status scan_launch(const ipcr_panel *p, ipcr_scratch *s, ipcr_genome *g) {
     s->cset ^= 1u;
     const uint64_t nblocks = pd.nblocks, block0 = pd.block0;
     trace("launch>", s);
+    // The lane.  A first attempt takes what ipcr_scratch_chain_after has chosen; a repeat from scan_collect (overflow redo,
+    // copy-path rescan) and the ranges of scan_segmented find nothing chosen and run on the scratch's OWN stream, unchained.
+    // Invariant that makes any lane safe: this scratch's previous launch -- on whichever lane it ran -- has RETIRED before
+    // this one is enqueued.  scan_collect waits for the launch's stop event (published scans) or for the marker behind its
+    // read-back (the others) before it returns or repeats, so the counter set the previous launch cleared for this one, the
+    // tickets and the hit buffer are at rest, and nothing of this scratch is left on the other lane.  Scans of OTHER scratches
+    // on either lane touch none of this scratch's buffers; the genome is read-only.
     const hipStream_t own = s->stream;
     const hipStream_t lane = s->lane_next ? s->lane_next->s : own;
     s->lane_used = s->lane_next ? std::move(s->lane_next) : s->own_lane;
     s->lane_next.reset();
+    s->lane_other = std::move(s->lane_other_next);
+    s->lane_other_next.reset();
+    pd.pred = std::move(s->pred_next);
+    s->pred_next.reset();
+    {   // a pair of events nobody measures against any more (a successor on the other lane may still hold the last one)
+        s->sweep_ev.reset();
+        for (const auto &e : s->sweep_evs)
+            if (e.use_count() == 1) { s->sweep_ev = e; break; }
+        if (!s->sweep_ev) {
+            auto e = std::make_shared<ipcr_scratch::SweepEv>();
+            HIPCHK(hipEventCreate(&e->start));
+            HIPCHK(hipEventCreate(&e->stop));
+            s->sweep_evs.push_back(e);
+            s->sweep_ev = std::move(e);
+        }
+        s->sweep_ev->frontier.reset();
+        s->ev[0] = s->sweep_ev->start;
+        s->ev[1] = s->sweep_ev->stop;
+    }
     pd.fused = false;
     pd.verified = false;
     pd.published = false;
@@ -2687,6 +2733,10 @@ ipcr_status scan_collect(const ipcr_panel *p, ipcr_scratch *s, ipcr_genome *g) {
             continue;
         }
         const uint64_t nhit = pc[1], ncand = pc[2], fullest = pc[3];
+        // A buffer overflowed: the scan is repeated (here, or in ranges by scan_segmented) on the scratch's own stream, which
+        // need not be the lane this attempt ran on -- and a published attempt has only handed over its counters, not retired.
+        // Wait for it (scan_launch: the invariant), so that no two launches of one scratch are ever in flight.
+        if ((fullest > s->qcap || nhit > s->hcap) && pd.published) HIPCHK(hipEventSynchronize(s->ev[1]));
         if (fullest > s->qcap) { // a queue segment overflowed: regrow all segments and rescan
             uint64_t want = s->qcap;
             while (want < fullest) want *= 2;
@@ -2773,7 +2823,7 @@ ipcr_status scan_collect(const ipcr_panel *p, ipcr_scratch *s, ipcr_genome *g) {
         if (nhit > got) HIPCHK(hipMemcpy(raw.data() + got, s->d_hits + got, (nhit - got) * sizeof(ipcr_hit), hipMemcpyDeviceToHost));
         s->prefix_hint = std::max<uint64_t>(256, nhit + nhit / 4 + 16);
         float fms = 0, vms = 0;
-        static const bool check_pub = env_flag("IPCR_DEBUG_PUBLISH_CHECK", false);
+        const bool check_pub = env_flag("IPCR_DEBUG_PUBLISH_CHECK", false); // (per call: a test turns it on for some passes)
         if (check_pub && pd.published && got) { // what the host took from pinned memory vs what the kernel left in device memory
             std::vector<ipcr_hit> dev(got);
             HIPCHK(hipMemcpy(dev.data(), s->d_hits, got * sizeof(ipcr_hit), hipMemcpyDeviceToHost));
@@ -2787,6 +2837,25 @@ ipcr_status scan_collect(const ipcr_panel *p, ipcr_scratch *s, ipcr_genome *g) {
         }
         trace("retired", s);
         HIPCHK(hipEventElapsedTime(&fms, s->ev[0], s->ev[1]));
+        if (pd.pred) {
+            // Chained on the other lane than its predecessor: the two sweeps overlap, and a launch's own start -> stop time
+            // would count the shared stretch twice.  filter_ms is the EXCLUSIVE time instead -- own end - max(own start, end
+            // of whatever sweep of the chain ended last so far) -- the time by which this sweep extended the device's busy
+            // period; over a window of chained passes these sum to the busy time.  0 if it ended under its predecessors.
+            // (the predecessor was enqueued first and is as a rule collected already: the wait is for its retirement at most)
+            const std::shared_ptr<ipcr_scratch::SweepEv> front = pd.pred->frontier ? pd.pred->frontier : pd.pred;
+            HIPCHK(hipEventSynchronize(front->stop));
+            float lead = 0; // own start -> the front's end
+            if (hipEventElapsedTime(&lead, s->ev[0], front->stop) != hipSuccess) { // (its launch failed before it was recorded)
+                (void)hipGetLastError();
+                lead = 0;
+            }
+            if (lead >= fms) { // ended under it: the front stays where it is
+                fms = 0;
+                s->sweep_ev->frontier = front;
+            } else if (lead > 0) fms -= lead;
+            pd.pred.reset();
+        }
         if (pd.verified) HIPCHK(hipEventElapsedTime(&vms, s->ev[2], s->ev[3]));
         s->stats.filter_ms = fms;
         s->stats.verify_ms = vms;
@@ -3166,7 +3235,8 @@ ipcr_status ipcr_scratch_create_on(const ipcr_panel *p, int32_t device, ipcr_scr
             }
         }
         raw->stream = raw->own_lane->s;
-        for (auto &e : raw->ev) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipEventCreate(&raw->ev[2])); // (ev[0] / ev[1]: the sweep's pair, made by scan_launch)
+        HIPCHK(hipEventCreate(&raw->ev[3]));
         raw->qcap = QCAP_INIT;
         raw->hcap = HCAP_INIT;
         HIPCHK(hipMalloc((void **)&raw->d_queue, raw->qcap * IPCR_QUEUE_SHARDS * sizeof(ipcr_queue_entry)));
@@ -3221,8 +3291,8 @@ void ipcr_scratch_destroy(ipcr_scratch *s) {
     if (s->d_probe_misc) (void)hipFree(s->d_probe_misc);
     if (s->pinned) (void)hipHostFree(s->pinned);
     if (s->d_tickets) (void)hipFree(s->d_tickets);
-    for (auto &e : s->ev)
-        if (e) (void)hipEventDestroy(e);
+    for (int e = 2; e < 4; ++e) // (the sweep pairs go with their last holder: a successor on the other lane may measure against one)
+        if (s->ev[e]) (void)hipEventDestroy(s->ev[e]);
     if (s->ev_done) (void)hipEventDestroy(s->ev_done);
     if (s->cstream) (void)hipStreamDestroy(s->cstream);
     if (s->probe_stream) (void)hipStreamDestroy(s->probe_stream);
@@ -3432,9 +3502,25 @@ ipcr_status ipcr_scratch_chain_after(ipcr_scratch *s, const ipcr_scratch *prev) 
     if (s == prev) return fail(IPCR_ERR_INVALID, "ipcr_scratch_chain_after: a scratch cannot follow itself");
     if (s->pend.active) return fail(IPCR_ERR_INVALID, "ipcr_scratch_chain_after: a scan is in flight on this scratch");
     if (s->device != prev->device) return fail(IPCR_ERR_INVALID, "ipcr_scratch_chain_after: scratches of different devices");
-    s->lane_next = prev->lane_used ? prev->lane_used : prev->own_lane; // stream order is the dependency
+    const std::shared_ptr<ipcr_scratch::Lane> &prev_lane = prev->lane_used ? prev->lane_used : prev->own_lane;
+    const char *lv = getenv("IPCR_CHAIN_LANES"); // per call: one process can run both forms
+    if (lv && *lv && atoi(lv) <= 1) { // one lane: stream order is the dependency
+        s->lane_next = prev_lane;
+        s->lane_other_next.reset();
+        s->pred_next.reset();
+        return IPCR_OK;
+    }
+    // two lanes: the lane prev did NOT use -- the chain's other lane if prev was itself chained, else (first link) this
+    // scratch's own stream.  No dependency between the two sweeps: they share nothing (scan_launch: the invariant).
+    s->lane_next = prev->lane_other ? prev->lane_other : s->own_lane;
+    s->lane_other_next = prev_lane;
+    // filter_ms of the scan is measured against prev's sweep if that one is in flight or was the last thing prev ran
+    s->pred_next = s->lane_next != prev_lane ? prev->sweep_ev : nullptr;
     return IPCR_OK;
 }
+
+// tests: the stream the scratch's last scan was enqueued on (null: none yet)
+void *ipcr_internal_scratch_lane(const ipcr_scratch *s) { return (s && s->lane_used) ? (void *)s->lane_used->s : nullptr; }
 
 ipcr_status ipcr_scan_genome_begin(const ipcr_panel *p, ipcr_scratch *s, const ipcr_genome *g) {
     ipcr_status st = scratch_ready(p, s);

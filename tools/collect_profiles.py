@@ -240,6 +240,14 @@ def readme_text():
             elif f.endswith(".json") and "_headline_ab" in f:  # alternating bench runs against the parent build
                 j = json.load(open(path))
                 row = "alternating `%s` runs, C2 Gbases/s: %s" % (j["cmd"], ", ".join("%s %s" % (k, " / ".join(_num(v) for v in vs)) for k, vs in j["headline"].items()))
+            elif f.endswith(".json") and "_chain_lanes_ab" in f:  # chained sweeps on two lanes against the parent build
+                j = json.load(open(path))
+                row = "alternating bench runs (%s), C2 Gbases/s / ms per step: %s; median gain %s %%, parent's range %s %%" % (
+                    j["command"].split(",")[0], "; ".join("%s %s" % (k, ", ".join("%s / %s" % (_num(r["value"], 5), _num(r["ms_per_step"])) for r in rs))
+                                                           for k, rs in j["runs"].items()),
+                    _num(j["median_gain_rel"] * 100, 3), _num(j["parent_range_rel"] * 100, 2))
+            elif f.endswith("_timeline.txt"):  # tools/kernel_timeline.py over a rocprofv3 --kernel-trace run
+                row = "`tools/kernel_timeline.py`, last line: " + open(path).read().strip().splitlines()[-1]
             if row is None and f.endswith("_stats.csv") and "_nested" in f:  # the nested probe under rocprofv3 --stats
                 with open(path, newline="") as fh:
                     rows = {r.get("Name", "").split("(")[0].replace("void ", ""): r for r in csv.DictReader(fh)}
