@@ -57,18 +57,8 @@ namespace {
 
 thread_local std::string g_err;
 
-ipcr_status fail(ipcr_status st, const char *fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return st;
-}
-
 } // namespace
-ipcr_status ipcr_internal_fail(ipcr_status st, const char *fmt, ...) { // for the other translation units
+ipcr_status ipcr_internal_fail(ipcr_status st, const char *fmt, ...) { // (external: the other translation units fail through it too)
     char buf[1024];
     va_list ap;
     va_start(ap, fmt);
@@ -78,6 +68,8 @@ ipcr_status ipcr_internal_fail(ipcr_status st, const char *fmt, ...) { // for th
     return st;
 }
 namespace {
+
+constexpr auto &fail = ipcr_internal_fail; // this file's name for it
 
 // ------------------------------------------------------------ devices
 // One host process may drive every GPU of a node: each scratch / genome belongs to a DEVICE SLOT, the panel keeps one set of
@@ -129,6 +121,22 @@ struct DeviceGuard {
     } while (0)
 
 bool env_flag(const char *name, bool dflt);
+
+// Grow-only buffers of device / pinned host memory: *p holds `need` bytes when these return hipSuccess.  One that is too
+// small is freed and made anew with `new_cap` bytes -- every caller's own growth rule, which decides how often its steady
+// state comes here: hipFree waits for the whole device.  After a failure the pointer is null and the capacity 0.
+hipError_t grow_buffer(void **p, uint64_t *cap, uint64_t need, uint64_t new_cap, bool pinned) {
+    if (need <= *cap) return hipSuccess;
+    if (*p) (void)(pinned ? hipHostFree(*p) : hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    const hipError_t e = pinned ? hipHostMalloc(p, new_cap, hipHostMallocDefault) : hipMalloc(p, new_cap);
+    if (e == hipSuccess) *cap = new_cap;
+    else *p = nullptr;
+    return e;
+}
+hipError_t grow_device(void **p, uint64_t *cap, uint64_t need, uint64_t new_cap) { return grow_buffer(p, cap, need, new_cap, false); }
+hipError_t grow_pinned(void **p, uint64_t *cap, uint64_t need, uint64_t new_cap) { return grow_buffer(p, cap, need, new_cap, true); }
 
 // ------------------------------------------------------------ the host's way into device memory
 // Large BAR: the whole of the device's memory is mapped into the host's address space, and the CPU's write-combining
@@ -1091,6 +1099,25 @@ uint64_t record_cols(uint64_t len) { // whole column pairs, with >= IPCR_PAD_BAS
     return ((len + IPCR_PAD_BASES + two - 1) / two) * 2ull;
 }
 
+// The genome's staging buffer with room for `need` bytes, of the kind asked for: fine-grained (the host writes it through the
+// BAR, and the device reads what has just been written past its L2, never a stale line) or any.  A buffer that is too
+// small -- or coarse-grained where fine-grained memory is wanted -- is freed and made anew with `new_cap` bytes, or as many as
+// it had if that is more.  g->staging_fine says in every case what g->staging is; after a failure there is no buffer
+// (capacity 0) and the caller decides what to fall back to.
+hipError_t genome_staging(ipcr_genome *g, uint64_t need, uint64_t new_cap, bool want_fine) {
+    if (need <= g->staging_cap && (g->staging_fine || !want_fine)) return hipSuccess;
+    if (g->staging) (void)hipFree(g->staging);
+    g->staging = nullptr;
+    g->staging_fine = false;
+    const uint64_t cap = std::max(g->staging_cap, new_cap);
+    g->staging_cap = 0;
+    const hipError_t e = want_fine ? hipExtMallocWithFlags((void **)&g->staging, cap, hipDeviceMallocFinegrained) : hipMalloc((void **)&g->staging, cap);
+    if (e != hipSuccess) { g->staging = nullptr; return e; }
+    g->staging_cap = cap;
+    g->staging_fine = want_fine;
+    return hipSuccess;
+}
+
 ipcr_status genome_alloc(ipcr_genome *g, uint64_t cap_cols, uint32_t max_records) {
     g->cap_cols = ((cap_cols + 63) / 64) * 64;
     g->max_records = max_records;
@@ -1424,6 +1451,57 @@ bool genome_any_reset(const ipcr_genome *g) {
     return false;
 }
 
+// what the join takes per record: bit 0 the record holds a reset byte, bit 1 some record of the genome does
+std::vector<uint8_t> genome_record_flags(const ipcr_genome *g) {
+    std::vector<uint8_t> fl(g->rec_start.size());
+    const bool any = genome_any_reset(g);
+    for (size_t r = 0; r < fl.size(); ++r) fl[r] = (uint8_t)((g->flags[r] & 1u) | (any ? 2u : 0u));
+    return fl;
+}
+
+// [a, b) of a record in the genome's padded coordinates: R is the record's first base, L its length.  a > b spans the origin:
+// record[a:] ++ record[:b], the amplicon of a wrap-around product (internal/pipeline/pipeline.go:80-89)
+struct Span {
+    uint64_t R = 0, L = 0, a = 0, b = 0;
+    uint64_t len() const { return a <= b ? b - a : (L - a) + b; }
+};
+
+// (record, start, end) as a caller gives them -> the span, or IPCR_ERR_INVALID: `what` names the entry point, `item` what it
+// calls the things it was given ("window", "site", "product") and `i` which of them this is
+ipcr_status resolve_span(const char *what, const char *item, size_t i, const ipcr_genome *g, int64_t record, int64_t start, int64_t end, Span *out) {
+    if (record < 0 || (size_t)record >= g->rec_len.size()) return fail(IPCR_ERR_INVALID, "%s: %s %zu: no record %lld", what, item, i, (long long)record);
+    const int64_t L = (int64_t)g->rec_len[(size_t)record];
+    if (start < 0 || end < 0 || start > L || end > L)
+        return fail(IPCR_ERR_INVALID, "%s: %s %zu [%lld, %lld) outside its record of %lld bases", what, item, i, (long long)start, (long long)end, (long long)L);
+    *out = Span{g->rec_start[(size_t)record], (uint64_t)L, (uint64_t)start, (uint64_t)end};
+    return IPCR_OK;
+}
+
+// the span's one or two parts as the gather and probe kernels take them, its bytes going to `out_off`
+ipcr_amp_seg span_seg(const Span &sp, uint64_t out_off) {
+    const bool wrap = sp.a > sp.b;
+    return ipcr_amp_seg{sp.R + sp.a, wrap ? sp.L - sp.a : sp.b - sp.a, sp.R, wrap ? sp.b : 0, out_off};
+}
+
+// What a reader of a resident genome's tiles begins with: padding and packing are complete (genome_finalize waits on the host
+// for the genome's own stream), under read_mu -- such readers may finalize from several threads.  With `nruns` the reader
+// decodes bytes and needs the exception runs: refused for a genome that keeps none.
+ipcr_status genome_reader_ready(const char *what, ipcr_genome *g, uint64_t *nruns) {
+    std::lock_guard<std::mutex> lk(g->read_mu);
+    const ipcr_status st = genome_finalize(g);
+    if (st != IPCR_OK || !nruns) return st;
+    if (g->exc_dropped) return fail(IPCR_ERR_UNSUPPORTED, "%s: the genome holds more than %llu exception runs and keeps none", what, (unsigned long long)g->exc_bound);
+    if (!g->exc_capture) return fail(IPCR_ERR_UNSUPPORTED, "%s: a scratch-private genome keeps no exception runs", what);
+    *nruns = g->exc_sorted;
+    return IPCR_OK;
+}
+
+// IPCR_TEST_SITE_PIECE / IPCR_TEST_THERMO_PIECE: tests lower the items a reader puts into one launch
+uint64_t test_piece(const char *name, uint64_t dflt) {
+    const char *e = getenv(name);
+    return (e && *e) ? std::min<uint64_t>(dflt, std::max<uint64_t>(1, strtoull(e, nullptr, 10))) : dflt;
+}
+
 } // namespace
 
 extern "C" {
@@ -1482,19 +1560,7 @@ static bool genome_add_host_packed(ipcr_genome *g, const uint8_t *seq, uint64_t 
     auto hip = [&](hipError_t e, const char *what) { if (e != hipSuccess && *st == IPCR_OK) *st = fail(IPCR_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e)); return e == hipSuccess; };
     constexpr uint64_t GROUP = 2048; // columns per group: 8 Mb
     const uint64_t gcols = std::min(cols, GROUP), dev_bytes = gcols * 2048ull;
-    if (dev_bytes > g->staging_cap || !g->staging_fine) {
-        if (g->staging) (void)hipFree(g->staging);
-        g->staging = nullptr;
-        g->staging_fine = false;
-        g->staging_cap = std::max(g->staging_cap, dev_bytes);
-        if (hipExtMallocWithFlags((void **)&g->staging, g->staging_cap, hipDeviceMallocFinegrained) != hipSuccess) {
-            (void)hipGetLastError();
-            g->staging = nullptr;
-            g->staging_cap = 0;
-            return false;
-        }
-        g->staging_fine = true;
-    }
+    if (genome_staging(g, dev_bytes, dev_bytes, true) != hipSuccess) { (void)hipGetLastError(); return false; } // (no such memory here)
     if (!g->h_planes) { // the invalid / reset planes of one group (pinned: a dirty group's DMA reads them)
         if (!hip(hipHostMalloc((void **)&g->h_planes, GROUP * 1024ull, hipHostMallocDefault), "hipHostMalloc")) return true;
     }
@@ -1703,13 +1769,8 @@ ipcr_status ipcr_genome_add_record(ipcr_genome *g, const uint8_t *seq, uint64_t 
         ipcr_status hst = IPCR_OK;
         if (genome_add_host_packed(g, seq, len, &hst)) return hst;
     }
-    if (len + 16 > g->staging_cap) {
-        if (g->staging) (void)hipFree(g->staging);
-        g->staging = nullptr;
-        g->staging_fine = false; // coarse-grained: the next host-packed record re-allocates it before writing through the BAR
-        g->staging_cap = len + 16 + (len >> 3);
-        HIPCHK(hipMalloc((void **)&g->staging, g->staging_cap));
-    }
+    // (coarse-grained if it is made here: the next host-packed record re-allocates it before writing through the BAR)
+    HIPCHK(genome_staging(g, len + 16, len + 16 + (len >> 3), false));
     if (len) HIPCHK(hipMemcpyAsync(g->staging, seq, len, hipMemcpyHostToDevice, g->stream));
     return genome_add_device(g, g->staging, len);
 }
@@ -1796,10 +1857,11 @@ struct ReadCtx {
     // kernel reports a byte without a complement through
     ipcr_site_dev *d_sites = nullptr, *h_sites = nullptr; // h_sites pinned
     unsigned long long *d_bad = nullptr, *h_bad = nullptr; // h_bad pinned
+    uint64_t d_sites_cap = 0, h_sites_cap = 0, d_bad_cap = 0, h_bad_cap = 0; // in bytes, as every capacity here
     // thermo_run (grown by its calls on this context, never shrunk): the ends of one piece, and the panel's primer table;
     // the scores of a piece land in d_out
     ipcr_thermo_end *d_ends = nullptr, *h_ends = nullptr; // h_ends pinned
-    uint64_t ends_cap = 0;                                // in products (two ends each)
+    uint64_t d_ends_cap = 0, h_ends_cap = 0;
     ipcr_thermo_primer *d_primers = nullptr;
     uint64_t primers_cap = 0;
 };
@@ -1842,32 +1904,22 @@ ipcr_status ipcr_genome_read_windows(const ipcr_genome *cg, const ipcr_window *w
     if (!cg || n < 0 || (n && !windows) || !offsets || !needed) return fail(IPCR_ERR_INVALID, "ipcr_genome_read_windows: null argument");
     ipcr_genome *g = const_cast<ipcr_genome *>(cg);
     offsets[0] = 0;
+    std::vector<Span> spans((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
-        const ipcr_window &w = windows[i];
-        if (w.record < 0 || (size_t)w.record >= g->rec_len.size()) return fail(IPCR_ERR_INVALID, "ipcr_genome_read_windows: window %lld: no record %d", (long long)i, w.record);
-        const int64_t L = (int64_t)g->rec_len[(size_t)w.record];
-        if (w.start < 0 || w.end < 0 || w.start > L || w.end > L)
-            return fail(IPCR_ERR_INVALID, "ipcr_genome_read_windows: window %lld [%lld, %lld) outside its record of %lld bases", (long long)i,
-                        (long long)w.start, (long long)w.end, (long long)L);
-        offsets[i + 1] = offsets[i] + (uint64_t)(w.start <= w.end ? w.end - w.start : (L - w.start) + w.end);
+        const ipcr_status ws = resolve_span("ipcr_genome_read_windows", "window", (size_t)i, g, windows[i].record, windows[i].start, windows[i].end, &spans[(size_t)i]);
+        if (ws != IPCR_OK) return ws;
+        offsets[i + 1] = offsets[i] + spans[(size_t)i].len();
     }
     *needed = offsets[n];
     if (cap < *needed) return fail(IPCR_ERR_CAPACITY, "ipcr_genome_read_windows: %llu bytes do not fit %llu", (unsigned long long)*needed, (unsigned long long)cap);
     DeviceGuard dg(g->device);
     uint64_t nruns = 0;
-    {
-        std::lock_guard<std::mutex> lk(g->read_mu);
-        const ipcr_status st = genome_finalize(g);
-        if (st != IPCR_OK) return st;
-        if (g->exc_dropped) return fail(IPCR_ERR_UNSUPPORTED, "ipcr_genome_read_windows: the genome holds more than %llu exception runs and keeps none",
-                                        (unsigned long long)g->exc_bound);
-        if (!g->exc_capture) return fail(IPCR_ERR_UNSUPPORTED, "ipcr_genome_read_windows: a scratch-private genome keeps no exception runs");
-        nruns = g->exc_sorted;
-    }
+    ipcr_status st = genome_reader_ready("ipcr_genome_read_windows", g, &nruns);
+    if (st != IPCR_OK) return st;
     if (*needed == 0) return IPCR_OK;
     if (!out) return fail(IPCR_ERR_INVALID, "ipcr_genome_read_windows: null output");
     ReadCtx *c = nullptr;
-    ipcr_status st = read_ctx_acquire(g->device, &c);
+    st = read_ctx_acquire(g->device, &c);
     if (st != IPCR_OK) return st;
     // pieces: consecutive segments whose bytes are consecutive in `out`; a piece is gathered, copied out and waited for
     uint64_t nseg = 0, piece0 = 0, piece_bytes = 0;
@@ -1884,11 +1936,9 @@ ipcr_status ipcr_genome_read_windows(const ipcr_genome *cg, const ipcr_window *w
     };
     hipError_t e = hipSuccess;
     for (int64_t i = 0; i < n && e == hipSuccess; ++i) {
-        const ipcr_window &w = windows[i];
-        const uint64_t R = g->rec_start[(size_t)w.record], L = g->rec_len[(size_t)w.record];
-        const uint64_t s0 = (uint64_t)w.start, e0 = (uint64_t)w.end;
-        // the window's pieces in padded coordinates: [R + start, R + end), or [R + start, R + L) ++ [R, R + end)
-        const uint64_t part_p[2] = {R + s0, R}, part_n[2] = {s0 <= e0 ? e0 - s0 : L - s0, s0 <= e0 ? 0 : e0};
+        // the window's parts in padded coordinates: [R + start, R + end), or [R + start, R + L) ++ [R, R + end)
+        const ipcr_amp_seg two = span_seg(spans[(size_t)i], 0);
+        const uint64_t part_p[2] = {two.pa, two.pb}, part_n[2] = {two.len_a, two.len_b};
         for (int k = 0; k < 2 && e == hipSuccess; ++k)
             for (uint64_t a = 0; a < part_n[k] && e == hipSuccess;) {
                 if (nseg == READ_PIECE_SEGS || piece_bytes == READ_PIECE_BYTES) e = flush();
@@ -1911,21 +1961,12 @@ namespace {
 
 // the site read's buffers of a context, made once
 ipcr_status read_ctx_site_buffers(ReadCtx *c) {
-    if (c->d_sites) return IPCR_OK;
-    ipcr_site_dev *d = nullptr, *h = nullptr;
-    unsigned long long *db = nullptr, *hb = nullptr;
-    hipError_t e = hipMalloc((void **)&d, READ_PIECE_SITES * sizeof(ipcr_site_dev));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&h, READ_PIECE_SITES * sizeof(ipcr_site_dev), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&db, 8);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&hb, 8, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
-        if (db) (void)hipFree(db);
-        if (hb) (void)hipHostFree(hb);
-        return fail(IPCR_ERR_DEVICE, "ipcr_genome_read_sites: %s", hipGetErrorString(e));
-    }
-    c->d_sites = d; c->h_sites = h; c->d_bad = db; c->h_bad = hb;
+    const uint64_t bytes = READ_PIECE_SITES * sizeof(ipcr_site_dev);
+    hipError_t e = grow_device((void **)&c->d_sites, &c->d_sites_cap, bytes, bytes);
+    if (e == hipSuccess) e = grow_pinned((void **)&c->h_sites, &c->h_sites_cap, bytes, bytes);
+    if (e == hipSuccess) e = grow_device((void **)&c->d_bad, &c->d_bad_cap, 8, 8);
+    if (e == hipSuccess) e = grow_pinned((void **)&c->h_bad, &c->h_bad_cap, 8, 8);
+    if (e != hipSuccess) return fail(IPCR_ERR_DEVICE, "ipcr_genome_read_sites: %s", hipGetErrorString(e)); // (what was made stays for the next call)
     return IPCR_OK;
 }
 
@@ -1935,13 +1976,11 @@ ipcr_status read_sites(const char *what, ipcr_genome *g, const ipcr_site *sites,
     offsets[0] = 0;
     for (int64_t i = 0; i < n; ++i) {
         const ipcr_site &s = sites[i];
-        if (s.record < 0 || (size_t)s.record >= g->rec_len.size()) return fail(IPCR_ERR_INVALID, "%s: site %lld: no record %d", what, (long long)i, s.record);
         if (s.len == 0 || s.len > IPCR_MAX_PRIMER_LEN)
             return fail(IPCR_ERR_INVALID, "%s: site %lld: length %u is not in 1..%d", what, (long long)i, (unsigned)s.len, IPCR_MAX_PRIMER_LEN);
-        const int64_t L = (int64_t)g->rec_len[(size_t)s.record];
-        if (s.pos < 0 || s.pos > L || (int64_t)s.len > L - s.pos)
-            return fail(IPCR_ERR_INVALID, "%s: site %lld [%lld, %lld) outside its record of %lld bases", what, (long long)i, (long long)s.pos,
-                        (long long)s.pos + s.len, (long long)L);
+        Span sp; // (a site never wraps; a position at the far end of int64 is outside every record)
+        const ipcr_status ss = resolve_span(what, "site", (size_t)i, g, s.record, s.pos, s.pos > INT64_MAX - s.len ? INT64_MAX : s.pos + s.len, &sp);
+        if (ss != IPCR_OK) return ss;
         offsets[i + 1] = offsets[i] + s.len;
     }
     *needed = offsets[n];
@@ -1949,21 +1988,12 @@ ipcr_status read_sites(const char *what, ipcr_genome *g, const ipcr_site *sites,
     if (n == 0) return IPCR_OK;
     DeviceGuard dg(g->device);
     uint64_t nruns = 0;
-    {
-        std::lock_guard<std::mutex> lk(g->read_mu);
-        const ipcr_status st = genome_finalize(g);
-        if (st != IPCR_OK) return st;
-        if (g->exc_dropped) return fail(IPCR_ERR_UNSUPPORTED, "%s: the genome holds more than %llu exception runs and keeps none", what,
-                                        (unsigned long long)g->exc_bound);
-        if (!g->exc_capture) return fail(IPCR_ERR_UNSUPPORTED, "%s: a scratch-private genome keeps no exception runs", what);
-        nruns = g->exc_sorted;
-    }
+    ipcr_status st = genome_reader_ready(what, g, &nruns);
+    if (st != IPCR_OK) return st;
     if (!out) return fail(IPCR_ERR_INVALID, "%s: null output", what);
-    uint64_t piece_sites = READ_PIECE_SITES;
-    if (const char *e = getenv("IPCR_TEST_SITE_PIECE"))
-        if (*e) piece_sites = std::min<uint64_t>(piece_sites, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
+    const uint64_t piece_sites = test_piece("IPCR_TEST_SITE_PIECE", READ_PIECE_SITES);
     ReadCtx *c = nullptr;
-    ipcr_status st = read_ctx_acquire(g->device, &c);
+    st = read_ctx_acquire(g->device, &c);
     if (st != IPCR_OK) return st;
     st = read_ctx_site_buffers(c);
     hipError_t e = hipSuccess;
@@ -2031,7 +2061,7 @@ uint8_t ipcr_genome_record_flags(const ipcr_genome *g, uint32_t record) {
         DeviceGuard dg(g->device);
         if (genome_finalize(const_cast<ipcr_genome *>(g)) != IPCR_OK) return 0;
     }
-    return (uint8_t)((g->flags[record] & 1u) | (genome_any_reset(g) ? 2u : 0u));
+    return genome_record_flags(g)[record];
 }
 
 } // extern "C"
@@ -2111,8 +2141,6 @@ struct ipcr_scratch {
     std::vector<ipcr_hit> hits_raw;  // in device append order
     std::vector<uint32_t> bucket;    // scratch of sort_hits
     std::vector<ipcr_product> products;
-    std::vector<uint64_t> last_rec_len; // of the last scanned genome (for probe)
-    std::vector<uint64_t> last_rec_start;
     ipcr_scan_stats stats{};
     std::vector<ipcr_chunk_window> windows; // of the last ipcr_scan_genome_chunked
     bool products_in_windows = false;       // ... whose products are the current ones: `record` = window, coordinates window-local
@@ -2660,8 +2688,6 @@ ipcr_status scan_enqueue(const ipcr_panel *p, ipcr_scratch *s, ipcr_genome *g, b
     ipcr_status st = chunk ? genome_finalize_async(g) : genome_finalize(g);
     if (st != IPCR_OK) return st;
     trace("finalized", s);
-    s->last_rec_len = g->rec_len;
-    s->last_rec_start = g->rec_start;
     const bool clean_chunks = !chunk || env_flag("IPCR_CHUNK_CLEAN_MODE", true); // (per call, for the same reason as IPCR_CHUNK_HOSTPACK)
     const bool any_reset = chunk ? (chunk_reset != 0 || !clean_chunks) : genome_any_reset(g);
     pd.mode = (!p->modes_equal && any_reset) ? 1 : 0;
@@ -3355,18 +3381,21 @@ ipcr_status ipcr_scan_genome_hits(const ipcr_panel *p, ipcr_scratch *s, const ip
     return scan_hits(p, s, const_cast<ipcr_genome *>(g));
 }
 
+// the tail of a scan over a resident genome whose hits have been collected: the join, and the times of a scan that began at t0
+static ipcr_status join_genome_hits(const ipcr_panel *p, ipcr_scratch *s, const ipcr_genome *g, ipcr_emit_fn emit, void *user,
+                                    std::chrono::steady_clock::time_point t0) {
+    const std::vector<uint8_t> fl = genome_record_flags(g);
+    const auto tj = std::chrono::steady_clock::now();
+    const ipcr_status st = join_sorted_hits(p, s, g->rec_len.data(), fl.data(), (uint32_t)fl.size(), emit, user);
+    s->stats.join_ms = ms_since(tj);
+    s->stats.total_ms = ms_since(t0);
+    return st;
+}
+
 ipcr_status ipcr_scan_genome(const ipcr_panel *p, ipcr_scratch *s, const ipcr_genome *g, ipcr_emit_fn emit, void *user) {
     const auto t0 = std::chrono::steady_clock::now();
-    ipcr_status st = ipcr_scan_genome_hits(p, s, g);
-    if (st != IPCR_OK) return st;
-    std::vector<uint8_t> fl(g->rec_start.size());
-    const bool any = genome_any_reset(g);
-    for (size_t r = 0; r < fl.size(); ++r) fl[r] = (uint8_t)((g->flags[r] & 1u) | (any ? 2u : 0u));
-    const auto tj = std::chrono::steady_clock::now();
-    st = join_sorted_hits(p, s, g->rec_len.data(), fl.data(), (uint32_t)fl.size(), emit, user);
-    s->stats.join_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tj).count();
-    s->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return st;
+    const ipcr_status st = ipcr_scan_genome_hits(p, s, g);
+    return st != IPCR_OK ? st : join_genome_hits(p, s, g, emit, user, t0);
 }
 
 // The rolling windows of one record, as the streaming reader emits them (fasta.cpp: ipcr_fasta_next; core/fasta/path_ctx.go:
@@ -3538,13 +3567,7 @@ ipcr_status ipcr_scan_genome_end(const ipcr_panel *p, ipcr_scratch *s, const ipc
     DeviceGuard dg(s->device);
     st = scan_collect(p, s, const_cast<ipcr_genome *>(g));
     if (st != IPCR_OK) return st;
-    std::vector<uint8_t> fl(g->rec_start.size());
-    const bool any = genome_any_reset(g);
-    for (size_t r = 0; r < fl.size(); ++r) fl[r] = (uint8_t)((g->flags[r] & 1u) | (any ? 2u : 0u));
-    const auto tj = std::chrono::steady_clock::now();
-    st = join_sorted_hits(p, s, g->rec_len.data(), fl.data(), (uint32_t)fl.size(), emit, user);
-    s->stats.join_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tj).count();
-    s->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s->pend.t0).count();
+    st = join_genome_hits(p, s, g, emit, user, s->pend.t0);
     trace("joined", s);
     return st;
 }
@@ -3567,9 +3590,8 @@ ipcr_status ipcr_join_hits(const ipcr_panel *p, ipcr_scratch *s, const ipcr_hit 
 // not by this core, and a plain memcpy's read-for-ownership of the destination lines costs a third of the memory
 // traffic (measured per 4 MB chunk with 8 threads copying at once: memcpy 0.27 ms, this 0.17 ms).
 static void stream_copy(uint8_t *dst, const uint8_t *src, uint64_t n) {
-    static const bool plain = getenv("IPCR_CHUNK_NTCOPY") && atoi(getenv("IPCR_CHUNK_NTCOPY")) == 0;
     uint64_t i = 0;
-    if (!plain && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+    if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
         for (; i + 64 <= n; i += 64) {
             const __m128i a = _mm_loadu_si128(reinterpret_cast<const __m128i *>(src + i));
             const __m128i b = _mm_loadu_si128(reinterpret_cast<const __m128i *>(src + i + 16));
@@ -3585,6 +3607,307 @@ static void stream_copy(uint8_t *dst, const uint8_t *src, uint64_t n) {
     if (i < n) memcpy(dst + i, src + i, n - i);
 }
 
+// ---- ipcr_scan_chunk, step by step.  What the steps share of one call:
+struct ChunkCall {
+    const ipcr_panel *p;
+    ipcr_scratch *s;
+    ipcr_genome *g;      // the scratch's private chunk genome; its stream is the scratch's
+    const uint8_t *seq;
+    uint64_t len;
+    int live;            // the panel's scratches alive: a lone worker, or a pool of them
+    BarInfo bar_info;
+    bool bar_on;         // the host's packer may write through the BAR
+};
+
+// A genome private to the scratch (*slot: its chunk, or the amplicons of its nested scan) made anew with room for `bases`
+// and `max_records`.  It lives on the scratch's stream: copy, pack, sweep and hand-over are one in-order sequence and the
+// host waits once, at the end.
+static ipcr_status scratch_private_genome(ipcr_scratch *s, ipcr_genome **slot, uint64_t bases, uint32_t max_records) {
+    if (*slot) ipcr_genome_destroy(*slot);
+    *slot = nullptr;
+    const ipcr_status st = ipcr_genome_create_on(bases, max_records, s->device, slot);
+    if (st != IPCR_OK) return st;
+    (*slot)->exc_capture = false; // (its caller holds the bytes)
+    (void)hipStreamDestroy((*slot)->stream);
+    (*slot)->stream = s->stream;
+    (*slot)->shared_stream = true;
+    return IPCR_OK;
+}
+
+// the scratch's chunk genome with room for `len` bases: made anew where the one it has is too small
+static ipcr_status chunk_genome(ipcr_scratch *s, uint64_t len) {
+    const uint64_t need_cols = record_cols(len) + 64;
+    if (s->chunk && s->chunk->cap_cols >= need_cols) return IPCR_OK;
+    const ipcr_status st = scratch_private_genome(s, &s->chunk, (need_cols + (need_cols >> 2)) * IPCR_COLUMN_BASES, 1);
+    if (st != IPCR_OK) return st;
+    HIPCHK(hipMemsetAsync(s->chunk->d_block_rec, 0, (s->chunk->cap_cols / 64 + 2) * 4ull, s->stream)); // one record: every block is record 0's
+    return IPCR_OK;
+}
+
+// a worker's own two pinned slabs and the events that say when the DMA has read them, made at their first use
+constexpr uint64_t CHUNK_SLAB_BYTES = 8ull << 20;
+static ipcr_status chunk_slabs(ipcr_scratch *s) {
+    for (int h = 0; h < 2; ++h) {
+        if (!s->h_stage[h]) HIPCHK(hipHostMalloc((void **)&s->h_stage[h], CHUNK_SLAB_BYTES, hipHostMallocDefault));
+        if (!s->ev_stage[h]) HIPCHK(hipEventCreateWithFlags(&s->ev_stage[h], hipEventDisableTiming));
+    }
+    return IPCR_OK;
+}
+
+// The host-packed send of one chunk: its slices, and what their packers found in them.  Slice i holds the columns
+// [gs[i], gs[i + 1]); its planes lie in a pinned slab as [lo | hi | inv | rst], each 128 words per column of the slice.
+struct PackedSend {
+    const ChunkCall &c;
+    bool bar;                      // this chunk goes through the BAR (the staging buffer is fine-grained)
+    uint64_t col0;                 // the record's first column in the genome
+    std::vector<uint64_t> gs;      // first columns of the slices (+ the end)
+    std::vector<uint32_t> sflags;  // per slice: pack_linear's flags (bit 0 a byte outside ACGTacgt, bit 1 lower case)
+    std::vector<uint32_t> colbits; // per slice, 64 words, one bit per column: its invalid plane has crossed the link
+    std::vector<uint8_t> marked;   // the slice's columns have been looked over by its packers
+    uint64_t nsl() const { return gs.size() - 1; }
+    uint32_t pack_cols(uint64_t i, uint8_t *slab, uint64_t c0, uint64_t nc) const;
+    void mark_columns(uint64_t i, const uint8_t *slab, uint64_t c0, uint64_t nc);
+    ipcr_status send_slice(uint64_t i, const uint8_t *slab);
+};
+
+// columns [c0, c0 + nc) of slice i into the slice's planes at `slab`
+// (bar: the two code planes go straight into the slice's place in device memory, write-only, through the BAR; the
+// invalid and reset planes stay in the pinned slab and follow only if the slice holds such a byte)
+uint32_t PackedSend::pack_cols(uint64_t i, uint8_t *slab, uint64_t c0, uint64_t nc) const {
+    const uint64_t s0 = gs[(size_t)i], snc = gs[(size_t)i + 1] - s0, W = snc * 128u, b0 = c0 * IPCR_COLUMN_BASES;
+    const uint64_t nb = b0 < c.len ? std::min<uint64_t>(c.len - b0, nc * IPCR_COLUMN_BASES) : 0;
+    uint32_t *w = reinterpret_cast<uint32_t *>(slab) + (c0 - s0) * 128u;
+    uint32_t *wd = bar ? reinterpret_cast<uint32_t *>(c.g->staging + s0 * 2048ull) + (c0 - s0) * 128u : w;
+    return ipcr::pack_linear(c.seq + (nb ? b0 : 0), nb, nc * IPCR_COLUMN_BASES, wd, wd + W, w + 2 * W, w + 3 * W);
+}
+
+// Runs of N are short and far between (a genome's 0.1 %: one column of 4096 bases in a hundred holds one): of a slice that
+// holds an invalid base only the columns whose invalid plane holds a bit cross the link -- 512 bytes each, through the BAR --
+// and a bitmap in the (unused) reset plane's place tells the conversion kernel which; it makes the others' bits itself.
+// Whoever packed the columns looks them over (the pool's threads for a lone worker's groups), the sender writes the bitmap.
+// (A slice that holds lower case, or more than 2048 columns, sends the whole plane instead: send_slice.)
+void PackedSend::mark_columns(uint64_t i, const uint8_t *slab, uint64_t c0, uint64_t nc) { // columns [c0, c0 + nc) of slice i
+    const uint64_t s0 = gs[(size_t)i], snc = gs[(size_t)i + 1] - s0, W = snc * 128u;
+    if (snc > 2048) return;
+    uint8_t *d = c.g->staging + s0 * 2048ull;
+    const uint32_t *hiv = reinterpret_cast<const uint32_t *>(slab) + 2 * W;
+    for (uint64_t col = c0 - s0; col < c0 - s0 + nc; ++col) {
+        uint32_t any = 0;
+        for (uint32_t k = 0; k < 128u; ++k) any |= hiv[col * 128u + k];
+        if (any) {
+            __atomic_fetch_or(&colbits[(size_t)i * 64u + (size_t)(col >> 5)], 1u << (col & 31u), __ATOMIC_RELAXED);
+            bar_copy(d + W * 8u + col * 512u, slab + W * 8u + col * 512u, 512u);
+        }
+    }
+}
+
+// slice i, packed at `slab`, on its way: what is left of its planes to cross the link, and its conversion launch
+ipcr_status PackedSend::send_slice(uint64_t i, const uint8_t *slab) { // the rst plane crosses the link only if the slice holds lower case
+    ipcr_genome *g = c.g;
+    const uint64_t c0 = gs[(size_t)i], nc = gs[(size_t)i + 1] - c0, W = nc * 128u;
+    const bool lower = (sflags[(size_t)i] & 2u) != 0;
+    const uint32_t *iv_cols = nullptr; // (device) one bit per column: its invalid plane has crossed the link
+    // ... and the invalid-bit plane only if it holds a byte outside ACGT at all: the conversion kernel knows where the
+    // record ends and makes the padding's bits itself (0.25 B/base on the link: IPCR_CHUNK_SKIP_INV=0 sends it always)
+    const bool need_inv = lower || (sflags[(size_t)i] & 1u) != 0 || !env_flag("IPCR_CHUNK_SKIP_INV", true);
+    uint8_t *d = g->staging + c0 * 2048ull;
+    // A lone caller: the conversion kernel reads the pinned slab over the link itself, no copy operation in between
+    // (whole 150 Mb record: 60 Gbases/s against 51).  A pool of workers keeps the copy engine: their kernels would
+    // otherwise wait on the link with the compute units held (16 workers: 78 Gbases/s against 99).
+    // IPCR_CHUNK_ZEROCOPY=0/1 forces.
+    static const int zc_env = getenv("IPCR_CHUNK_ZEROCOPY") ? atoi(getenv("IPCR_CHUNK_ZEROCOPY")) : -1;
+    const bool zerocopy = !bar && (zc_env >= 0 ? zc_env != 0 : c.live <= 1);
+    if (bar) { // the code planes are there already; the other two follow only if the slice needs them -- through the BAR as well
+        // (a copy operation per dirty chunk cost a stream of chunks with N a third of its rate: 16 workers 108 Gbases/s against 157)
+        if (need_inv) {
+            if (lower || nc > 2048) bar_copy(d + W * 8u, slab + W * 8u, W * 4u * (lower ? 2u : 1u));
+            else {
+                if (!marked[(size_t)i]) mark_columns(i, slab, c0, nc); // (a worker's own slice: nobody has looked yet)
+                alignas(64) uint32_t bits[64];
+                memcpy(bits, &colbits[(size_t)i * 64u], sizeof bits);
+                bar_copy(d + W * 12u, reinterpret_cast<const uint8_t *>(bits), sizeof bits);
+                iv_cols = reinterpret_cast<const uint32_t *>(d + W * 12u);
+            }
+        }
+        bar_flush(c.bar_info);
+    } else if (!zerocopy) HIPCHK(hipMemcpyAsync(d, slab, W * 4u * (lower ? 4u : need_inv ? 3u : 2u), hipMemcpyHostToDevice, g->stream));
+    const uint32_t *dl = zerocopy ? reinterpret_cast<const uint32_t *>(slab) : reinterpret_cast<const uint32_t *>(d);
+    HIPCHK(ipcr::launch_tiles_from_linear(g->stream, dl, dl + W, need_inv ? dl + 2 * W : nullptr, lower ? dl + 3 * W : nullptr, col0, col0 + c0, nc, c.len,
+                                          g->planes, g->rst, g->d_colmask, i == 0 ? g->d_rec_start : nullptr, i == 0 ? g->d_rec_len : nullptr,
+                                          i == 0 ? g->e0 : nullptr, i + 1 == nsl() ? g->e1 : nullptr, iv_cols));
+    return IPCR_OK;
+}
+
+// a worker of a pool: its own two pinned slabs, slice i + 1 is packed while slice i crosses the link
+static ipcr_status chunk_send_own_slabs(PackedSend &ps) {
+    ipcr_scratch *s = ps.c.s;
+    ipcr_status st = chunk_slabs(s);
+    for (uint64_t i = 0; i < ps.nsl() && st == IPCR_OK; ++i) {
+        const int h = (int)(i & 1u);
+        if (i >= 2) HIPCHK(hipEventSynchronize(s->ev_stage[h])); // the DMA that read this slab has finished
+        ps.sflags[(size_t)i] = ps.pack_cols(i, s->h_stage[h], ps.gs[(size_t)i], ps.gs[(size_t)i + 1] - ps.gs[(size_t)i]);
+        st = ps.send_slice(i, s->h_stage[h]);
+        if (st == IPCR_OK && i + 2 < ps.nsl()) HIPCHK(hipEventRecord(s->ev_stage[h], ps.c.g->stream));
+    }
+    return st;
+}
+
+// A LONE worker (internal/pipeline/pipeline.go:60-125 with Threads = 1; a genome of few large records): a GROUP of
+// columns is packed by the process's pool, every thread a run of its columns into the group's planes, and sent as
+// ONE conversion launch that reads the pinned planes over the link itself; the next group is packed under it.  Two
+// groups for a 4 Mb chunk (pack 0 | pack 1 under transfer 0 | transfer 1, sweep), 8 Mb groups for a chromosome.
+static ipcr_status chunk_send_pooled(PackedSend &ps, uint64_t plane_bytes) {
+    ipcr_scratch *s = ps.c.s;
+    const uint64_t nsl = ps.nsl();
+    HIPCHK(grow_pinned((void **)&s->h_planes, &s->h_planes_cap, plane_bytes, plane_bytes + (plane_bytes >> 3)));
+    // ONE pool run over the items of all groups, group by group; the caller's thread does not pack: it sends group i
+    // (one conversion launch that reads the pinned planes over the link) the moment the group's last item is done, while
+    // the pool is already packing group i + 1
+    const uint64_t nthreads = std::max<uint64_t>(1, PackPool::get().size() - 1);
+    struct Item { uint64_t group, c0, nc; };
+    std::vector<Item> items;
+    std::vector<uint32_t> group_items((size_t)nsl, 0);
+    for (uint64_t i = 0; i < nsl; ++i) {
+        const uint64_t c0 = ps.gs[(size_t)i], nc = ps.gs[(size_t)i + 1] - c0;
+        const uint64_t per = std::max<uint64_t>(32, ((nc + nthreads - 1) / nthreads + 7) / 8 * 8); // columns per item: 128 KB of bases at least
+        for (uint64_t a = c0; a < c0 + nc; a += per) { items.push_back({i, a, std::min<uint64_t>(per, c0 + nc - a)}); ++group_items[(size_t)i]; }
+    }
+    std::vector<uint32_t> iflags(items.size(), 0);
+    std::unique_ptr<std::atomic<uint32_t>[]> group_done(new std::atomic<uint32_t>[(size_t)nsl]);
+    for (uint64_t i = 0; i < nsl; ++i) group_done[(size_t)i].store(0);
+    uint64_t sent = 0;
+    ipcr_status send_st = IPCR_OK;
+    auto send_ready = [&]() {
+        while (sent < nsl && send_st == IPCR_OK && group_done[(size_t)sent].load(std::memory_order_acquire) == group_items[(size_t)sent]) {
+            for (size_t k = 0; k < items.size(); ++k)
+                if (items[k].group == sent) ps.sflags[(size_t)sent] |= iflags[k];
+            trace("group packed", s);
+            send_st = ps.send_slice(sent, s->h_planes + ps.gs[(size_t)sent] * 2048ull);
+            ++sent;
+        }
+    };
+    const std::function<void()> idle = send_ready;
+    trace("pack>", s);
+    static const bool item_times = getenv("IPCR_DEBUG_TIMES") != nullptr;
+    std::vector<double> it0(item_times ? items.size() : 0), it1(item_times ? items.size() : 0);
+    std::vector<int> itcpu(item_times ? items.size() : 0);
+    if (ps.bar) std::fill(ps.marked.begin(), ps.marked.end(), (uint8_t)1); // (every item looks its own columns over)
+    const auto tp0 = std::chrono::steady_clock::now();
+    PackPool::get().run(items.size(), [&](size_t k) {
+        const Item &it = items[k];
+        uint8_t *slab = s->h_planes + ps.gs[(size_t)it.group] * 2048ull;
+        if (item_times) { it0[k] = ms_since(tp0) * 1000.0; itcpu[k] = sched_getcpu(); }
+        iflags[k] = ps.pack_cols(it.group, slab, it.c0, it.nc);
+        if (ps.bar && (iflags[k] & 1u)) ps.mark_columns(it.group, slab, it.c0, it.nc);
+        if (item_times) it1[k] = ms_since(tp0) * 1000.0;
+        group_done[(size_t)it.group].fetch_add(1, std::memory_order_release);
+    }, slot_phys(ps.c.g->device), &idle);
+    send_ready();
+    if (item_times)
+        for (size_t k = 0; k < items.size(); ++k)
+            fprintf(stderr, "    item %2zu group %llu cols %4llu cpu %3d: %6.1f .. %6.1f us\n", k, (unsigned long long)items[k].group,
+                    (unsigned long long)items[k].nc, itcpu[k], it0[k], it1[k]);
+    return send_st;
+}
+
+// The bases packed on the host into 2-bit + invalid-bit planes, slice by slice, and the tiles made from them on the device;
+// *pinned_flag: the record holds a byte outside ACGTacgt
+static ipcr_status chunk_send_packed(const ChunkCall &c, uint32_t *pinned_flag) {
+    ipcr_genome *g = c.g;
+    const auto th0 = std::chrono::steady_clock::now();
+    const uint64_t cols = record_cols(c.len), col0 = g->next_col;
+    if (g->rec_start.size() >= g->max_records || col0 + cols > g->cap_cols) return fail(IPCR_ERR_CAPACITY, "chunk genome capacity exceeded");
+    const uint64_t dev_bytes = cols * 2048ull; // four planes x 128 words per column
+    hipError_t se = genome_staging(g, dev_bytes, dev_bytes + (dev_bytes >> 3), c.bar_on);
+    if (se != hipSuccess && c.bar_on) { // no fine-grained memory here: pinned slabs + DMA from now on
+        (void)hipGetLastError();
+        host_writable_off(slot_phys(g->device));
+        se = genome_staging(g, dev_bytes, dev_bytes + (dev_bytes >> 3), false);
+    }
+    if (se != hipSuccess) return fail(IPCR_ERR_DEVICE, "ipcr_scan_chunk: staging buffer of %llu bytes: %s", (unsigned long long)dev_bytes, hipGetErrorString(se));
+    const bool pooled = c.live <= 1 && PackPool::get().size() > 1 && cols >= 64;
+    PackedSend ps{c, c.bar_on && g->staging_fine, col0, {}, {}, {}, {}};
+    // columns per slice: up to 1024 = 4 Mbases, i.e. a worker's 4 Mb chunk is ONE copy + ONE conversion launch.  Cutting it
+    // in two or four (the first part crosses the link while the next is packed) was slower under a
+    // pool -- 16 workers: 94 / 72 / 49 Gbases/s for 1 / 2 / 4 parts -- every operation on a stream costs its dispatch latency
+    const uint64_t SLC = pooled ? 2048 : std::min<uint64_t>(1024, std::max<uint64_t>(128, cols));
+    // first columns of the slices (+ the end).  The lone worker's chunk of up to 8 Mb goes as TWO groups, three quarters and
+    // a quarter: what follows the packing on the device -- the last group's way over the link, its conversion -- is then
+    // short, and the first group's transfer hides under the packing of the second
+    if (pooled && cols <= 2048 && cols >= 256) { // (one group instead, now that the packer writes through the BAR: no difference, 47-52 Gbases/s either way)
+        const uint64_t first = std::min<uint64_t>(cols - 64, (cols * 3 / 4 + 7) / 8 * 8);
+        ps.gs = {0, first, cols};
+    } else {
+        for (uint64_t c0 = 0; c0 < cols; c0 += SLC) ps.gs.push_back(c0);
+        ps.gs.push_back(cols);
+    }
+    ps.sflags.assign((size_t)ps.nsl(), 0);
+    ps.colbits.assign((size_t)ps.nsl() * 64u, 0);
+    ps.marked.assign((size_t)ps.nsl(), 0);
+    const ipcr_status st = pooled ? chunk_send_pooled(ps, dev_bytes) : chunk_send_own_slabs(ps);
+    if (st != IPCR_OK) return st;
+    uint32_t fl = 0;
+    for (uint32_t f : ps.sflags) fl |= f;
+    *pinned_flag = fl & 1u;
+    genome_account_record(g, c.len, cols);
+    c.s->stats.hostpack_ms = ms_since(th0);
+    return IPCR_OK;
+}
+
+// The bases as ASCII into the genome's staging buffer, packed by the device; *pinned_flag arrives when the stream has passed the pack.
+// One worker: the runtime's pageable copy (it pins the caller's pages in place) runs at the link rate.  Several
+// workers calling it at once serialise inside the runtime (8 workers x 4 Mb chunks: 12 Gbases/s in all, a single
+// worker 22): then every worker stages through its own pinned slices instead.  IPCR_CHUNK_STAGING=0/1 forces.
+static ipcr_status chunk_send_ascii(const ChunkCall &c, uint32_t *pinned_flag) {
+    ipcr_scratch *s = c.s;
+    ipcr_genome *g = c.g;
+    const uint64_t len = c.len;
+    static const int force = getenv("IPCR_CHUNK_STAGING") ? atoi(getenv("IPCR_CHUNK_STAGING")) : -1;
+    const bool staged = force >= 0 ? force != 0 : c.live > 1;
+    // (coarse-grained if it is made here: the next host-packed record re-allocates it before writing through the BAR)
+    HIPCHK(genome_staging(g, len + 16, len + 16 + (len >> 3), false));
+    if (len && !staged) HIPCHK(hipMemcpyAsync(g->staging, c.seq, len, hipMemcpyHostToDevice, g->stream));
+    if (len && staged) {
+        // A chunk of up to 8 MiB goes in two halves: the DMA of the first runs under the CPU copy of the second, and
+        // two slices need no marker between them (8 workers x 4 Mb chunks: one slice 49.0, two 50.6, four 49.3
+        // Gbases/s; every further operation on the stream costs its own dispatch latency).  Anything larger -- a
+        // whole chromosome -- is double-buffered in 8 MiB slices.
+        const uint64_t halves = ((len + 1) / 2 + 4095) & ~4095ull;
+        const uint64_t SLICE = len <= CHUNK_SLAB_BYTES ? std::max<uint64_t>(halves, 65536) : CHUNK_SLAB_BYTES;
+        const ipcr_status st = chunk_slabs(s);
+        if (st != IPCR_OK) return st;
+        uint64_t i = 0;
+        for (uint64_t off = 0; off < len; off += SLICE, ++i) {
+            const int h = (int)(i & 1u);
+            const uint64_t n = std::min<uint64_t>(SLICE, len - off);
+            if (i >= 2) HIPCHK(hipEventSynchronize(s->ev_stage[h])); // the DMA that read this slice has finished
+            stream_copy(s->h_stage[h], c.seq + off, n);
+            HIPCHK(hipMemcpyAsync(g->staging + off, s->h_stage[h], n, hipMemcpyHostToDevice, g->stream));
+            if (off + 2 * SLICE < len) HIPCHK(hipEventRecord(s->ev_stage[h], g->stream)); // slice i + 2 will wait for it; a chunk of one or two slices needs no marker
+        }
+    }
+    return genome_add_device(g, len ? g->staging : nullptr, len, false, pinned_flag);
+}
+
+// the collected scan's hits joined, the chunk's flags and the call's times (it began at t0) put down
+static ipcr_status chunk_join(const ChunkCall &c, ipcr_emit_fn emit, void *user, std::chrono::steady_clock::time_point t0) {
+    ipcr_scratch *s = c.s;
+    ipcr_genome *g = c.g;
+    {
+        float ms = 0; // the pack kernel's events lie in front of the sweep on the same stream
+        HIPCHK(hipEventElapsedTime(&ms, g->e0, g->e1));
+        g->pack_ms += ms;
+        s->stats.pack_ms = ms;
+    }
+    g->flags.assign(1, (uint8_t)(pinned_seq(s)[4] & 1u));
+    g->flags_valid = true;
+    const uint8_t fl = (uint8_t)((g->flags[0] & 1u) | (s->pend.mode == 1 ? 2u : 0u));
+    const ipcr_status st = join_sorted_hits(c.p, s, g->rec_len.data(), &fl, 1, emit, user);
+    s->last_was_chunk = st == IPCR_OK; // the products' amplicons lie in s->chunk until the next scan (ipcr_probe_scratch_products)
+    s->stats.total_ms = ms_since(t0);
+    return st;
+}
+
 ipcr_status ipcr_scan_chunk(const ipcr_panel *p, ipcr_scratch *s, const uint8_t *seq, uint64_t len,
                             ipcr_emit_fn emit, void *user) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -3598,24 +3921,12 @@ ipcr_status ipcr_scan_chunk(const ipcr_panel *p, ipcr_scratch *s, const uint8_t 
     s->last_was_chunk = p->id.empty();
     if (p->id.empty()) return IPCR_OK; // compiled.go:163-165
     DeviceGuard dg(s->device); // the worker's thread may never have selected a device (a goroutine on any thread)
-    const uint64_t need_cols = record_cols(len) + 64;
-    if (!s->chunk || s->chunk->cap_cols < need_cols) {
-        if (s->chunk) ipcr_genome_destroy(s->chunk);
-        s->chunk = nullptr;
-        st = ipcr_genome_create_on((need_cols + (need_cols >> 2)) * IPCR_COLUMN_BASES, 1, s->device, &s->chunk);
-        if (st != IPCR_OK) return st;
-        s->chunk->exc_capture = false; // (its caller holds the bytes)
-        // the private chunk genome lives on the scratch's stream: copy, pack, sweep and hand-over are one
-        // in-order sequence and the host waits once, at the end
-        (void)hipStreamDestroy(s->chunk->stream);
-        s->chunk->stream = s->stream;
-        s->chunk->shared_stream = true;
-        HIPCHK(hipMemsetAsync(s->chunk->d_block_rec, 0, (s->chunk->cap_cols / 64 + 2) * 4ull, s->stream)); // one record: every block is record 0's
-    }
+    st = chunk_genome(s, len);
+    if (st != IPCR_OK) return st;
     ipcr_genome *g = s->chunk;
     genome_clear(g, true);
-    // Whatever goes wrong between here and the hand-over -- any early return below -- no DMA and no kernel may still read the
-    // caller's bytes or a pinned slab when the call returns: the caller may free the one, the next call rewrites the other.
+    // Whatever goes wrong between here and the hand-over -- any early return below, in any of the steps -- no DMA and no kernel may
+    // still read the caller's bytes or a pinned slab when the call returns: the caller may free the one, the next call rewrites the other.
     struct Drain {
         hipStream_t st;
         bool armed = true;
@@ -3623,7 +3934,8 @@ ipcr_status ipcr_scan_chunk(const ipcr_panel *p, ipcr_scratch *s, const uint8_t 
     } drain{g->stream};
     uint32_t *pinned_flag = pinned_seq(s) + 4; // set when the record holds a byte outside ACGTacgt (by the pack kernel, or by the host's packer)
     *pinned_flag = 0u;
-    const int live = p->live_scratches->load(std::memory_order_relaxed);
+    const BarInfo bar_info = device_bar(slot_phys(g->device));
+    const ChunkCall c{p, s, g, seq, len, p->live_scratches->load(std::memory_order_relaxed), bar_info, bar_info.writable && env_flag("IPCR_CHUNK_BAR", true)};
     // How the bases reach the device.  (a) Packed on the host into 2-bit + invalid-bit planes while they are staged in
     // pinned memory -- 0.375 bytes per base on the link instead of 1 (hostpack.cpp), tiles made from them on the device:
     // what a pool of workers does (every worker packs its own chunk), and a single worker with a record of 16 Mb or more
@@ -3635,263 +3947,41 @@ ipcr_status ipcr_scan_chunk(const ipcr_panel *p, ipcr_scratch *s, const uint8_t 
     // (c) Where the packer writes through the PCIe BAR (round 4) it is the faster way at EVERY size -- a lone worker's 50 kb / 150 kb /
     // 400 kb / 900 kb chunks: 45 / 47 / 56 / 58 us per call against 59 / 57 / 72 / 93 as ASCII -- and the chunk's reset flag is known
     // before the sweep is launched.
-    const BarInfo bar_info = device_bar(slot_phys(g->device));
-    const bool bar_on = bar_info.writable && env_flag("IPCR_CHUNK_BAR", true);
-    const bool hostpack = hp_env >= 0 ? hp_env != 0 : (ipcr::pack_linear_is_simd() && (bar_on || live > 1 || (len >= (1ull << 20) && PackPool::get().size() > 1) || len >= (16ull << 20)));
-    if (hostpack) {
-        const auto th0 = std::chrono::steady_clock::now();
-        const uint64_t cols = record_cols(len), col0 = g->next_col;
-        if (g->rec_start.size() >= g->max_records || col0 + cols > g->cap_cols) return fail(IPCR_ERR_CAPACITY, "chunk genome capacity exceeded");
-        const uint64_t dev_bytes = cols * 2048ull; // four planes x 128 words per column
-        bool bar = bar_on;
-        if (dev_bytes > g->staging_cap || (bar && !g->staging_fine)) {
-            if (g->staging) (void)hipFree(g->staging);
-            g->staging = nullptr;
-            g->staging_fine = false;
-            g->staging_cap = std::max(g->staging_cap, dev_bytes + (dev_bytes >> 3));
-            // fine-grained: the device reads what the host has just written through the BAR past its L2, never a stale line
-            if (bar && hipExtMallocWithFlags((void **)&g->staging, g->staging_cap, hipDeviceMallocFinegrained) == hipSuccess) g->staging_fine = true;
-            else {
-                if (bar) { (void)hipGetLastError(); host_writable_off(slot_phys(g->device)); } // no such memory here: pinned slabs + DMA from now on
-                g->staging = nullptr;
-                HIPCHK(hipMalloc((void **)&g->staging, g->staging_cap));
-            }
-        }
-        bar = bar && g->staging_fine;
-        const bool pooled = live <= 1 && PackPool::get().size() > 1 && cols >= 64;
-        // columns per slice: up to 1024 = 4 Mbases, i.e. a worker's 4 Mb chunk is ONE copy + ONE conversion launch.  Cutting it
-        // in two or four (IPCR_CHUNK_SPLIT: the first part crosses the link while the next is packed) was slower under a
-        // pool -- 16 workers: 94 / 72 / 49 Gbases/s for 1 / 2 / 4 parts -- every operation on a stream costs its dispatch latency
-        static const uint64_t split_env = getenv("IPCR_CHUNK_SPLIT") ? strtoull(getenv("IPCR_CHUNK_SPLIT"), nullptr, 10) : 1;
-        // A LONE worker (internal/pipeline/pipeline.go:60-125 with Threads = 1; a genome of few large records): a GROUP of
-        // columns is packed by the process's pool, every thread a run of its columns into the group's planes, and sent as
-        // ONE conversion launch that reads the pinned planes over the link itself; the next group is packed under it.  Two
-        // groups for a 4 Mb chunk (pack 0 | pack 1 under transfer 0 | transfer 1, sweep), 8 Mb groups for a chromosome.
-        const uint64_t SLC = pooled ? 2048 : std::min<uint64_t>(1024, std::max<uint64_t>(128, (cols + split_env - 1) / std::max<uint64_t>(split_env, 1)));
-        // first columns of the slices (+ the end).  The lone worker's chunk of up to 8 Mb goes as TWO groups, three quarters and
-        // a quarter: what follows the packing on the device -- the last group's way over the link, its conversion -- is then
-        // short, and the first group's transfer hides under the packing of the second
-        std::vector<uint64_t> gs;
-        if (pooled && cols <= 2048 && cols >= 256) { // (one group instead, now that the packer writes through the BAR: no difference, 47-52 Gbases/s either way)
-            const uint64_t first = std::min<uint64_t>(cols - 64, (cols * 3 / 4 + 7) / 8 * 8);
-            gs = {0, first, cols};
-        } else {
-            for (uint64_t c = 0; c < cols; c += SLC) gs.push_back(c);
-            gs.push_back(cols);
-        }
-        const uint64_t nsl = gs.size() - 1;
-        std::vector<uint32_t> sflags((size_t)nsl, 0);
-        // columns [c0, c0 + nc) of slice i (whose first column is gs[i] and which holds snc columns) into the slice's planes
-        // at `slab`: [lo | hi | inv | rst], snc x 128 words each
-        // (bar: the two code planes go straight into the slice's place in device memory, write-only, through the BAR; the
-        // invalid and reset planes stay in the pinned slab and follow by DMA only if the slice holds such a byte)
-        auto pack_cols = [&](uint64_t i, uint8_t *slab, uint64_t c0, uint64_t nc) -> uint32_t {
-            const uint64_t s0 = gs[(size_t)i], snc = gs[(size_t)i + 1] - s0, W = snc * 128u, b0 = c0 * IPCR_COLUMN_BASES;
-            const uint64_t nb = b0 < len ? std::min<uint64_t>(len - b0, nc * IPCR_COLUMN_BASES) : 0;
-            uint32_t *w = reinterpret_cast<uint32_t *>(slab) + (c0 - s0) * 128u;
-            uint32_t *wd = bar ? reinterpret_cast<uint32_t *>(g->staging + s0 * 2048ull) + (c0 - s0) * 128u : w;
-            return ipcr::pack_linear(seq + (nb ? b0 : 0), nb, nc * IPCR_COLUMN_BASES, wd, wd + W, w + 2 * W, w + 3 * W);
-        };
-        auto pack_slice = [&](uint64_t i, uint8_t *slab) { // planes of slice i: [lo | hi | inv | rst], nc x 128 words each
-            const uint64_t c0 = gs[(size_t)i], nc = gs[(size_t)i + 1] - c0;
-            sflags[(size_t)i] = pack_cols(i, slab, c0, nc);
-        };
-        // Runs of N are short and far between (a genome's 0.1 %: one column of 4096 bases in a hundred holds one): of a slice that
-        // holds an invalid base only the columns whose invalid plane holds a bit cross the link -- 512 bytes each, through the BAR --
-        // and a bitmap in the (unused) reset plane's place tells the conversion kernel which; it makes the others' bits itself.
-        // Whoever packed the columns looks them over (the pool's threads for a lone worker's groups), the sender writes the bitmap.
-        static const bool inv_cols = env_flag("IPCR_CHUNK_INV_COLUMNS", true);
-        std::vector<uint32_t> colbits((size_t)nsl * 64u, 0);
-        auto mark_columns = [&](uint64_t i, const uint8_t *slab, uint64_t c0, uint64_t nc) { // columns [c0, c0 + nc) of slice i
-            const uint64_t s0 = gs[(size_t)i], snc = gs[(size_t)i + 1] - s0, W = snc * 128u;
-            if (snc > 2048) return;
-            uint8_t *d = g->staging + s0 * 2048ull;
-            const uint32_t *hiv = reinterpret_cast<const uint32_t *>(slab) + 2 * W;
-            for (uint64_t c = c0 - s0; c < c0 - s0 + nc; ++c) {
-                uint32_t any = 0;
-                for (uint32_t k = 0; k < 128u; ++k) any |= hiv[c * 128u + k];
-                if (any) {
-                    __atomic_fetch_or(&colbits[(size_t)i * 64u + (size_t)(c >> 5)], 1u << (c & 31u), __ATOMIC_RELAXED);
-                    bar_copy(d + W * 8u + c * 512u, slab + W * 8u + c * 512u, 512u);
-                }
-            }
-        };
-        std::vector<uint8_t> marked((size_t)nsl, 0); // the slice's columns have been looked over by its packers
-        auto send_slice = [&](uint64_t i, const uint8_t *slab) -> ipcr_status { // the rst plane crosses the link only if the slice holds lower case
-            const uint64_t c0 = gs[(size_t)i], nc = gs[(size_t)i + 1] - c0, W = nc * 128u;
-            const bool lower = (sflags[(size_t)i] & 2u) != 0;
-            const uint32_t *iv_cols = nullptr; // (device) one bit per column: its invalid plane has crossed the link
-            // ... and the invalid-bit plane only if it holds a byte outside ACGT at all: the conversion kernel knows where the
-            // record ends and makes the padding's bits itself (0.25 B/base on the link: IPCR_CHUNK_SKIP_INV=0 sends it always)
-            const bool need_inv = lower || (sflags[(size_t)i] & 1u) != 0 || !env_flag("IPCR_CHUNK_SKIP_INV", true);
-            uint8_t *d = g->staging + c0 * 2048ull;
-            // A lone caller: the conversion kernel reads the pinned slab over the link itself, no copy operation in between
-            // (whole 150 Mb record: 60 Gbases/s against 51).  A pool of workers keeps the copy engine: their kernels would
-            // otherwise wait on the link with the compute units held (16 workers: 78 Gbases/s against 99).
-            // IPCR_CHUNK_ZEROCOPY=0/1 forces.
-            static const int zc_env = getenv("IPCR_CHUNK_ZEROCOPY") ? atoi(getenv("IPCR_CHUNK_ZEROCOPY")) : -1;
-            const bool zerocopy = !bar && (zc_env >= 0 ? zc_env != 0 : live <= 1);
-            if (bar) { // the code planes are there already; the other two follow only if the slice needs them -- through the BAR as well
-                // (a copy operation per dirty chunk cost a stream of chunks with N a third of its rate: 16 workers 108 Gbases/s against 157)
-                if (need_inv) {
-                    static const bool inv_dma = env_flag("IPCR_CHUNK_INV_DMA", false);
-                    if (inv_dma) HIPCHK(hipMemcpyAsync(d + W * 8u, slab + W * 8u, W * 4u * (lower ? 2u : 1u), hipMemcpyHostToDevice, g->stream));
-                    else if (lower || !inv_cols || nc > 2048) bar_copy(d + W * 8u, slab + W * 8u, W * 4u * (lower ? 2u : 1u));
-                    else {
-                        if (!marked[(size_t)i]) mark_columns(i, slab, c0, nc); // (a worker's own slice: nobody has looked yet)
-                        alignas(64) uint32_t bits[64];
-                        memcpy(bits, &colbits[(size_t)i * 64u], sizeof bits);
-                        bar_copy(d + W * 12u, reinterpret_cast<const uint8_t *>(bits), sizeof bits);
-                        iv_cols = reinterpret_cast<const uint32_t *>(d + W * 12u);
-                    }
-                }
-                bar_flush(bar_info);
-            } else if (!zerocopy) HIPCHK(hipMemcpyAsync(d, slab, W * 4u * (lower ? 4u : need_inv ? 3u : 2u), hipMemcpyHostToDevice, g->stream));
-            const uint32_t *dl = zerocopy ? reinterpret_cast<const uint32_t *>(slab) : reinterpret_cast<const uint32_t *>(d);
-            HIPCHK(ipcr::launch_tiles_from_linear(g->stream, dl, dl + W, need_inv ? dl + 2 * W : nullptr, lower ? dl + 3 * W : nullptr, col0, col0 + c0, nc, len,
-                                                  g->planes, g->rst, g->d_colmask, i == 0 ? g->d_rec_start : nullptr, i == 0 ? g->d_rec_len : nullptr,
-                                                  i == 0 ? g->e0 : nullptr, i + 1 == nsl ? g->e1 : nullptr, iv_cols));
-            return IPCR_OK;
-        };
-        if (!pooled) { // this worker's own two pinned slices: slice i + 1 is packed while slice i crosses the link
-            constexpr uint64_t SLAB = 8ull << 20;
-            for (int h = 0; h < 2; ++h) {
-                if (!s->h_stage[h]) HIPCHK(hipHostMalloc((void **)&s->h_stage[h], SLAB, hipHostMallocDefault));
-                if (!s->ev_stage[h]) HIPCHK(hipEventCreateWithFlags(&s->ev_stage[h], hipEventDisableTiming));
-            }
-            for (uint64_t i = 0; i < nsl; ++i) {
-                const int h = (int)(i & 1u);
-                if (i >= 2) HIPCHK(hipEventSynchronize(s->ev_stage[h])); // the DMA that read this slab has finished
-                pack_slice(i, s->h_stage[h]);
-                st = send_slice(i, s->h_stage[h]);
-                if (st != IPCR_OK) return st;
-                if (i + 2 < nsl) HIPCHK(hipEventRecord(s->ev_stage[h], g->stream));
-            }
-        } else { // one worker: the pool packs group i + 1 while group i crosses the link
-            if (dev_bytes > s->h_planes_cap) {
-                if (s->h_planes) (void)hipHostFree(s->h_planes);
-                s->h_planes = nullptr;
-                s->h_planes_cap = dev_bytes + (dev_bytes >> 3);
-                HIPCHK(hipHostMalloc((void **)&s->h_planes, s->h_planes_cap, hipHostMallocDefault));
-            }
-            // ONE pool run over the items of all groups, group by group; the caller's thread does not pack: it sends group i
-            // (one conversion launch that reads the pinned planes over the link) the moment the group's last item is done, while
-            // the pool is already packing group i + 1
-            const uint64_t nthreads = std::max<uint64_t>(1, PackPool::get().size() - 1);
-            struct Item { uint64_t group, c0, nc; };
-            std::vector<Item> items;
-            std::vector<uint32_t> group_items((size_t)nsl, 0);
-            for (uint64_t i = 0; i < nsl; ++i) {
-                const uint64_t c0 = gs[(size_t)i], nc = gs[(size_t)i + 1] - c0;
-                const uint64_t per = std::max<uint64_t>(32, ((nc + nthreads - 1) / nthreads + 7) / 8 * 8); // columns per item: 128 KB of bases at least
-                for (uint64_t a = c0; a < c0 + nc; a += per) { items.push_back({i, a, std::min<uint64_t>(per, c0 + nc - a)}); ++group_items[(size_t)i]; }
-            }
-            std::vector<uint32_t> iflags(items.size(), 0);
-            std::unique_ptr<std::atomic<uint32_t>[]> group_done(new std::atomic<uint32_t>[(size_t)nsl]);
-            for (uint64_t i = 0; i < nsl; ++i) group_done[(size_t)i].store(0);
-            uint64_t sent = 0;
-            ipcr_status send_st = IPCR_OK;
-            auto send_ready = [&]() {
-                while (sent < nsl && send_st == IPCR_OK && group_done[(size_t)sent].load(std::memory_order_acquire) == group_items[(size_t)sent]) {
-                    for (size_t k = 0; k < items.size(); ++k)
-                        if (items[k].group == sent) sflags[(size_t)sent] |= iflags[k];
-                    trace("group packed", s);
-                    send_st = send_slice(sent, s->h_planes + gs[(size_t)sent] * 2048ull);
-                    ++sent;
-                }
-            };
-            const std::function<void()> idle = send_ready;
-            trace("pack>", s);
-            static const bool item_times = getenv("IPCR_DEBUG_TIMES") != nullptr;
-            std::vector<double> it0(item_times ? items.size() : 0), it1(item_times ? items.size() : 0);
-            std::vector<int> itcpu(item_times ? items.size() : 0);
-            if (bar && inv_cols) std::fill(marked.begin(), marked.end(), (uint8_t)1); // (every item looks its own columns over)
-            const auto tp0 = std::chrono::steady_clock::now();
-            PackPool::get().run(items.size(), [&](size_t k) {
-                const Item &it = items[k];
-                if (item_times) { it0[k] = ms_since(tp0) * 1000.0; itcpu[k] = sched_getcpu(); }
-                iflags[k] = pack_cols(it.group, s->h_planes + gs[(size_t)it.group] * 2048ull, it.c0, it.nc);
-                if (bar && inv_cols && (iflags[k] & 1u)) mark_columns(it.group, s->h_planes + gs[(size_t)it.group] * 2048ull, it.c0, it.nc);
-                if (item_times) it1[k] = ms_since(tp0) * 1000.0;
-                group_done[(size_t)it.group].fetch_add(1, std::memory_order_release);
-            }, slot_phys(g->device), &idle);
-            send_ready();
-            if (item_times)
-                for (size_t k = 0; k < items.size(); ++k)
-                    fprintf(stderr, "    item %2zu group %llu cols %4llu cpu %3d: %6.1f .. %6.1f us\n", k, (unsigned long long)items[k].group,
-                            (unsigned long long)items[k].nc, itcpu[k], it0[k], it1[k]);
-            if (send_st != IPCR_OK) return send_st;
-        }
-        uint32_t fl = 0;
-        for (uint32_t f : sflags) fl |= f;
-        *pinned_flag = fl & 1u;
-        genome_account_record(g, len, cols);
-        s->stats.hostpack_ms = ms_since(th0);
-    } else {
-    constexpr uint64_t SLICE_MAX = 8ull << 20;
-    // One worker: the runtime's pageable copy (it pins the caller's pages in place) runs at the link rate.  Several
-    // workers calling it at once serialise inside the runtime (8 workers x 4 Mb chunks: 12 Gbases/s in all, a single
-    // worker 22): then every worker stages through its own pinned slices instead.  IPCR_CHUNK_STAGING=0/1 forces.
-    static const int force = getenv("IPCR_CHUNK_STAGING") ? atoi(getenv("IPCR_CHUNK_STAGING")) : -1;
-    const bool staged = force >= 0 ? force != 0 : live > 1;
-    const uint8_t *pack_src = nullptr;
-    if (len + 16 > g->staging_cap) {
-        if (g->staging) (void)hipFree(g->staging);
-        g->staging = nullptr;
-        g->staging_fine = false; // coarse-grained: the next host-packed record re-allocates it before writing through the BAR
-        g->staging_cap = len + 16 + (len >> 3);
-        HIPCHK(hipMalloc((void **)&g->staging, g->staging_cap));
-    }
-    if (len) {
-        pack_src = g->staging;
-        if (!staged) {
-            HIPCHK(hipMemcpyAsync(g->staging, seq, len, hipMemcpyHostToDevice, g->stream));
-        } else {
-            static const uint64_t slice_env = getenv("IPCR_CHUNK_SLICE") ? strtoull(getenv("IPCR_CHUNK_SLICE"), nullptr, 10) : 0;
-            // A chunk of up to 8 MiB goes in two halves: the DMA of the first runs under the CPU copy of the second, and
-            // two slices need no marker between them (8 workers x 4 Mb chunks: one slice 49.0, two 50.6, four 49.3
-            // Gbases/s; every further operation on the stream costs its own dispatch latency).  Anything larger -- a
-            // whole chromosome -- is double-buffered in 8 MiB slices.
-            const uint64_t halves = ((len + 1) / 2 + 4095) & ~4095ull;
-            const uint64_t SLICE = slice_env ? std::min<uint64_t>(std::max<uint64_t>(slice_env, 65536), SLICE_MAX)
-                                             : (len <= SLICE_MAX ? std::max<uint64_t>(halves, 65536) : SLICE_MAX);
-            for (int h = 0; h < 2; ++h) {
-                if (!s->h_stage[h]) HIPCHK(hipHostMalloc((void **)&s->h_stage[h], SLICE_MAX, hipHostMallocDefault));
-                if (!s->ev_stage[h]) HIPCHK(hipEventCreateWithFlags(&s->ev_stage[h], hipEventDisableTiming));
-            }
-            uint64_t i = 0;
-            for (uint64_t off = 0; off < len; off += SLICE, ++i) {
-                const int h = (int)(i & 1u);
-                const uint64_t n = std::min<uint64_t>(SLICE, len - off);
-                if (i >= 2) HIPCHK(hipEventSynchronize(s->ev_stage[h])); // the DMA that read this slice has finished
-                stream_copy(s->h_stage[h], seq + off, n);
-                HIPCHK(hipMemcpyAsync(g->staging + off, s->h_stage[h], n, hipMemcpyHostToDevice, g->stream));
-                if (off + 2 * SLICE < len) HIPCHK(hipEventRecord(s->ev_stage[h], g->stream)); // slice i + 2 will wait for it; a chunk of one or two slices needs no marker
-            }
-        }
-    }
-    st = genome_add_device(g, pack_src, len, false, pinned_flag);
+    const bool hostpack = hp_env >= 0 ? hp_env != 0 : (ipcr::pack_linear_is_simd() && (c.bar_on || c.live > 1 || (len >= (1ull << 20) && PackPool::get().size() > 1) || len >= (16ull << 20)));
+    st = hostpack ? chunk_send_packed(c, pinned_flag) : chunk_send_ascii(c, pinned_flag);
     if (st != IPCR_OK) return st;
-    }
     const double hostpack_keep = s->stats.hostpack_ms; // (scan_enqueue starts the statistics afresh)
     st = scan_enqueue(p, s, g, true, hostpack ? (int)(*pinned_flag & 1u) : -1);
     if (st == IPCR_OK) st = scan_collect(p, s, g);
     if (st != IPCR_OK) return st;
     drain.armed = false; // the scan has been collected: the stream has passed everything this call queued
     s->stats.hostpack_ms = hostpack_keep;
-    {
-        float ms = 0; // the pack kernel's events lie in front of the sweep on the same stream
-        HIPCHK(hipEventElapsedTime(&ms, g->e0, g->e1));
-        g->pack_ms += ms;
-        s->stats.pack_ms = ms;
+    return chunk_join(c, emit, user, t0);
+}
+
+// The products of the last scan on `outer` as windows of the genome their amplicons lie in, in record coordinates: the one place
+// that puts the window-local products of an ipcr_scan_genome_chunked (`in_windows`) back into their records.  A caller whose
+// products are chunk-local -- those of an ipcr_scan_chunk, read from the scratch's own chunk genome -- passes false.
+static std::vector<ipcr_window> product_windows(const ipcr_scratch *outer, bool in_windows) {
+    const size_t n = outer->products.size();
+    std::vector<ipcr_window> w(n);
+    for (size_t i = 0; i < n; ++i) {
+        const ipcr_product &pr = outer->products[i];
+        w[i].start = pr.start;
+        w[i].end = pr.end;
+        w[i].record = pr.record;
+        w[i].reserved = 0;
+        // products of ipcr_scan_genome_chunked: `record` is a window, coordinates are window-local
+        if (in_windows && pr.record >= 0 && (size_t)pr.record < outer->windows.size()) {
+            const ipcr_chunk_window &cw = outer->windows[(size_t)pr.record];
+            w[i].record = (int32_t)cw.record;
+            w[i].start += (int64_t)cw.start;
+            w[i].end += (int64_t)cw.start;
+        } else if (in_windows) {
+            w[i].record = -1; // (no window of that index: resolve_span refuses it, no such record)
+        }
     }
-    g->flags.assign(1, (uint8_t)(pinned_seq(s)[4] & 1u));
-    g->flags_valid = true;
-    const uint8_t fl = (uint8_t)((g->flags[0] & 1u) | (s->pend.mode == 1 ? 2u : 0u));
-    st = join_sorted_hits(p, s, g->rec_len.data(), &fl, 1, emit, user);
-    s->last_was_chunk = st == IPCR_OK; // the products' amplicons lie in s->chunk until the next scan (ipcr_probe_scratch_products)
-    s->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return st;
+    return w;
 }
 
 // ------------------------------------------------------------------------------ probe
@@ -3957,12 +4047,8 @@ static ipcr_status probe_ctx_acquire(int slot, uint64_t amp_len, ProbeCtx **out)
     }
     const uint64_t need = PROBE_CTX_AMP_OFF + amp_len + 64;
     if (need > c->hcap) { // (first use, or an amplicon beyond 64 KB: --max-length is 2000 by default)
-        if (c->h) (void)hipHostFree(c->h);
-        c->h = nullptr;
-        c->hcap = std::max<uint64_t>(need + (need >> 2), 64u << 10);
-        const hipError_t e = hipHostMalloc((void **)&c->h, c->hcap, hipHostMallocDefault);
+        const hipError_t e = grow_pinned((void **)&c->h, &c->hcap, need, std::max<uint64_t>(need + (need >> 2), 64u << 10));
         if (e != hipSuccess) {
-            c->hcap = 0;
             std::lock_guard<std::mutex> lk(g_probe_mu);
             g_probe_free.push_back(c);
             return fail(IPCR_ERR_DEVICE, "hipHostMalloc: %s", hipGetErrorString(e));
@@ -3975,6 +4061,23 @@ static ipcr_status probe_ctx_acquire(int slot, uint64_t amp_len, ProbeCtx **out)
 static void probe_ctx_release(ProbeCtx *c) {
     std::lock_guard<std::mutex> lk(g_probe_mu);
     g_probe_free.push_back(c);
+}
+
+// Waits for a result record that a kernel queued on `st` writes into pinned memory as ONE 16-byte store whose first word carries
+// `tag` above bit 0 (a kernel of a few waves: microseconds): spins on the tag, pausing at first and yielding later; now and
+// then asks the stream, and when that has drained looks once more.  false: the record has not come -- *q is then the
+// stream's error, or hipSuccess if it drained without the record.
+static bool wait_tagged(const volatile int32_t *rec, uint32_t tag, hipStream_t st, hipError_t *q) {
+    auto there = [&] { return ((uint32_t)__atomic_load_n(rec, __ATOMIC_ACQUIRE) >> 1) == tag; };
+    for (uint64_t spin = 1; !there(); ++spin) {
+        if (spin < 0x4000u) __builtin_ia32_pause();
+        else std::this_thread::yield();
+        if ((spin & 0x3FFFu) == 0) {
+            *q = hipStreamQuery(st);
+            if (*q != hipErrorNotReady) return there(); // the stream has drained
+        }
+    }
+    return true;
 }
 
 ipcr_status ipcr_probe_best_hit(const uint8_t *amplicon, uint64_t len, const char *probe, int32_t max_mm,
@@ -4004,22 +4107,10 @@ ipcr_status ipcr_probe_best_hit(const uint8_t *amplicon, uint64_t len, const cha
     const hipError_t le = ipcr::launch_probe(c->st, c->h + PROBE_CTX_AMP_OFF, offs, 1, c->h, c->h + 128, (uint32_t)prb.size(),
                                              (uint32_t)(max_mm < 0 ? 0 : max_mm), fast, reinterpret_cast<ipcr_probe_rec *>(c->h + 256), tag);
     if (le != hipSuccess) { probe_ctx_release(c); return fail(IPCR_ERR_DEVICE, "probe kernel: %s", hipGetErrorString(le)); }
-    // the record is one 16-byte store into pinned memory: spin on its tag (a kernel of one wave: microseconds)
-    bool got = false;
-    for (uint64_t spin = 1;; ++spin) {
-        if (((uint32_t)__atomic_load_n(res, __ATOMIC_ACQUIRE) >> 1) == tag) { got = true; break; }
-        if (spin < 0x4000u) __builtin_ia32_pause();
-        else std::this_thread::yield();
-        if ((spin & 0x3FFFu) == 0) {
-            const hipError_t q = hipStreamQuery(c->st);
-            if (q == hipErrorNotReady) continue;
-            got = ((uint32_t)__atomic_load_n(res, __ATOMIC_ACQUIRE) >> 1) == tag; // the stream has drained
-            if (!got) {
-                probe_ctx_release(c);
-                return fail(IPCR_ERR_DEVICE, "probe kernel: %s", q == hipSuccess ? "its result did not reach pinned memory" : hipGetErrorString(q));
-            }
-            break;
-        }
+    hipError_t q = hipSuccess;
+    if (!wait_tagged(res, tag, c->st, &q)) {
+        probe_ctx_release(c);
+        return fail(IPCR_ERR_DEVICE, "probe kernel: %s", q == hipSuccess ? "its result did not reach pinned memory" : hipGetErrorString(q));
     }
     std::atomic_thread_fence(std::memory_order_acquire);
     out->found = res[0] & 1;
@@ -4049,21 +4140,12 @@ ipcr_status ipcr_probe_products_end(ipcr_scratch *s, ipcr_probe_hit *out, int64_
     if (n == 0) return IPCR_OK;
     if (s->probe_res_off == 0) { memset(out, 0, (size_t)n * sizeof *out); return IPCR_OK; } // empty probe: nothing found (oligo.go:21-23)
     DeviceGuard dg(s->device);
-    // every record is ONE tagged 16-byte store into pinned memory: spin on the tags (a handful of products per chunk)
+    // one tagged record per product (a handful of products per chunk)
     const volatile int32_t *res = reinterpret_cast<const volatile int32_t *>(s->h_probe + s->probe_res_off);
-    const uint32_t tag = s->probe_tag;
-    for (int64_t i = 0; i < n; ++i) {
-        for (uint64_t spin = 1; ((uint32_t)__atomic_load_n(res + 4 * i, __ATOMIC_ACQUIRE) >> 1) != tag; ++spin) {
-            if (spin < 0x4000u) __builtin_ia32_pause();
-            else std::this_thread::yield();
-            if ((spin & 0x3FFFu) == 0) {
-                const hipError_t q = hipStreamQuery(s->probe_on);
-                if (q == hipErrorNotReady) continue;
-                if (((uint32_t)__atomic_load_n(res + 4 * i, __ATOMIC_ACQUIRE) >> 1) == tag) break; // the stream has drained
-                return fail(IPCR_ERR_DEVICE, "probe rescan: %s", q == hipSuccess ? "its results did not reach pinned memory" : hipGetErrorString(q));
-            }
-        }
-    }
+    hipError_t q = hipSuccess;
+    for (int64_t i = 0; i < n; ++i)
+        if (!wait_tagged(res + 4 * i, s->probe_tag, s->probe_on, &q))
+            return fail(IPCR_ERR_DEVICE, "probe rescan: %s", q == hipSuccess ? "its results did not reach pinned memory" : hipGetErrorString(q));
     std::atomic_thread_fence(std::memory_order_acquire);
     for (int64_t i = 0; i < n; ++i) { // (ipcr_probe_rec is layout-identical; the tag rides above bit 0 of `found`)
         out[i].found = res[4 * i] & 1;
@@ -4091,36 +4173,20 @@ static ipcr_status probe_begin(ipcr_scratch *s, const ipcr_genome *g, const char
     // pinned block: [0, 256) probe / rc masks | results | segments | offsets
     const uint64_t res_off = 256, seg_off = (res_off + n * sizeof(ipcr_probe_rec) + 15) & ~15ull;
     const uint64_t off_off = seg_off + n * sizeof(ipcr_amp_seg), hbytes = off_off + (n + 1) * 8;
-    if (hbytes > s->h_probe_cap) {
-        if (s->h_probe) (void)hipHostFree(s->h_probe);
-        s->h_probe = nullptr;
-        s->h_probe_cap = hbytes * 2;
-        HIPCHK(hipHostMalloc((void **)&s->h_probe, s->h_probe_cap, hipHostMallocDefault));
-    }
+    HIPCHK(grow_pinned((void **)&s->h_probe, &s->h_probe_cap, hbytes, hbytes * 2));
     if (!s->probe_stream) HIPCHK(hipStreamCreateWithFlags(&s->probe_stream, hipStreamNonBlocking));
     // amplicon = record[start:end], or record[start:] ++ record[:end] for wrap-around products
     // (internal/pipeline/pipeline.go:80-89)
     ipcr_amp_seg *segs = reinterpret_cast<ipcr_amp_seg *>(s->h_probe + seg_off);
     uint64_t *offs = reinterpret_cast<uint64_t *>(s->h_probe + off_off);
     offs[0] = 0;
+    const std::vector<ipcr_window> w = product_windows(s, s->products_in_windows && g != s->chunk); // (a chunk's products are chunk-local as they are)
     for (size_t i = 0; i < n; ++i) {
-        ipcr_product pr = s->products[i];
-        if (s->products_in_windows && g != s->chunk) { // products of ipcr_scan_genome_chunked: `record` is a window, coordinates are window-local
-            if (pr.record < 0 || (size_t)pr.record >= s->windows.size()) return fail(IPCR_ERR_INVALID, "product window outside the window list");
-            const ipcr_chunk_window &cw = s->windows[(size_t)pr.record];
-            pr.record = (int32_t)cw.record;
-            pr.start += (int64_t)cw.start;
-            pr.end += (int64_t)cw.start;
-        }
-        if ((size_t)pr.record >= g->rec_start.size()) return fail(IPCR_ERR_INVALID, "product record outside genome");
-        const uint64_t rs = g->rec_start[(size_t)pr.record], rl = g->rec_len[(size_t)pr.record];
-        if (pr.start < 0 || pr.end < 0 || (uint64_t)pr.start > rl || (uint64_t)pr.end > rl) return fail(IPCR_ERR_INVALID, "product outside its record");
-        ipcr_amp_seg sg{};
-        if (pr.start <= pr.end) { sg.pa = rs + (uint64_t)pr.start; sg.len_a = (uint64_t)(pr.end - pr.start); sg.pb = rs; sg.len_b = 0; }
-        else { sg.pa = rs + (uint64_t)pr.start; sg.len_a = rl - (uint64_t)pr.start; sg.pb = rs; sg.len_b = (uint64_t)pr.end; }
-        sg.out_off = offs[i];
-        offs[i + 1] = offs[i] + sg.len_a + sg.len_b;
-        segs[i] = sg;
+        Span sp;
+        st = resolve_span("ipcr_probe_products", "product", i, g, w[i].record, w[i].start, w[i].end, &sp);
+        if (st != IPCR_OK) return st;
+        segs[i] = span_seg(sp, offs[i]);
+        offs[i + 1] = offs[i] + sp.len();
     }
     const uint64_t amp_bytes = offs[n] + 16;
     uint64_t longest = 0;
@@ -4137,13 +4203,8 @@ static ipcr_status probe_begin(ipcr_scratch *s, const ipcr_genome *g, const char
         HIPCHK(ipcr::launch_probe_tiles(pst, g->planes, g->rst, segs, (uint32_t)n, s->h_probe, s->h_probe + 128, (uint32_t)prb.size(),
                                         (uint32_t)(max_mm < 0 ? 0 : max_mm), fast, res, s->probe_tag));
     } else { // an amplicon beyond the kernel's LDS stage (--max-length above 16 384): gathered to device memory first
-        if (amp_bytes > s->amps_cap) {
-            // (grows to the largest batch seen and stays: hipFree waits for the device, so a steady state must not come here)
-            if (s->d_amps) (void)hipFree(s->d_amps);
-            s->d_amps = nullptr;
-            s->amps_cap = std::max<uint64_t>(amp_bytes + (amp_bytes >> 1), 1u << 20);
-            HIPCHK(hipMalloc((void **)&s->d_amps, s->amps_cap));
-        }
+        // (grows to the largest batch seen and stays: hipFree waits for the device, so a steady state must not come here)
+        HIPCHK(grow_device((void **)&s->d_amps, &s->amps_cap, amp_bytes, std::max<uint64_t>(amp_bytes + (amp_bytes >> 1), 1u << 20)));
         HIPCHK(ipcr::launch_gather(pst, g->planes, g->rst, segs, (uint32_t)n, s->d_amps));
         HIPCHK(ipcr::launch_probe(pst, s->d_amps, offs, (uint32_t)n, s->h_probe, s->h_probe + 128, (uint32_t)prb.size(),
                                   (uint32_t)(max_mm < 0 ? 0 : max_mm), fast, res, s->probe_tag));
@@ -4205,46 +4266,25 @@ static ipcr_status nested_run(const ipcr_genome *g, const ipcr_window *windows, 
     std::vector<uint64_t> offs(n), lens(n);
     uint64_t off = 0, cols = 0;
     for (size_t i = 0; i < n; ++i) {
-        const ipcr_window &w = windows[i];
-        if (w.record < 0 || (size_t)w.record >= g->rec_start.size()) return fail(IPCR_ERR_INVALID, "window %zu: record outside the genome", i);
-        const uint64_t rs = g->rec_start[(size_t)w.record], rl = g->rec_len[(size_t)w.record];
-        if (w.start < 0 || w.end < 0 || (uint64_t)w.start > rl || (uint64_t)w.end > rl) return fail(IPCR_ERR_INVALID, "window %zu outside its record", i);
-        ipcr_amp_seg sg{};
-        if (w.start <= w.end) { sg.pa = rs + (uint64_t)w.start; sg.len_a = (uint64_t)(w.end - w.start); sg.pb = rs; sg.len_b = 0; }
-        else { sg.pa = rs + (uint64_t)w.start; sg.len_a = rl - (uint64_t)w.start; sg.pb = rs; sg.len_b = (uint64_t)w.end; }
-        sg.out_off = off;
+        Span sp;
+        st = resolve_span("ipcr_nested_windows", "window", i, g, windows[i].record, windows[i].start, windows[i].end, &sp);
+        if (st != IPCR_OK) return st;
+        segs[i] = span_seg(sp, off);
         offs[i] = off;
-        lens[i] = sg.len_a + sg.len_b;
+        lens[i] = sp.len();
         off = (off + lens[i] + 15) & ~15ull;
         cols += record_cols(lens[i]);
-        segs[i] = sg;
     }
-    if (off + 16 > s->amps_cap) {
-        if (s->d_amps) (void)hipFree(s->d_amps);
-        s->d_amps = nullptr;
-        s->amps_cap = off + 16 + (off >> 2);
-        HIPCHK(hipMalloc((void **)&s->d_amps, s->amps_cap));
-    }
+    HIPCHK(grow_device((void **)&s->d_amps, &s->amps_cap, off + 16, off + 16 + (off >> 2)));
     const uint64_t misc_bytes = n * (sizeof(ipcr_amp_seg) + sizeof(ipcr_pack_rec) + 4) + 256;
-    if (misc_bytes > s->probe_misc_cap) {
-        if (s->d_probe_misc) (void)hipFree(s->d_probe_misc);
-        s->d_probe_misc = nullptr;
-        s->probe_misc_cap = misc_bytes * 2;
-        HIPCHK(hipMalloc(&s->d_probe_misc, s->probe_misc_cap));
-    }
+    HIPCHK(grow_device(&s->d_probe_misc, &s->probe_misc_cap, misc_bytes, misc_bytes * 2));
     ipcr_amp_seg *dsegs = static_cast<ipcr_amp_seg *>(s->d_probe_misc);
     HIPCHK(hipMemcpyAsync(dsegs, segs.data(), n * sizeof(ipcr_amp_seg), hipMemcpyHostToDevice, s->stream));
     HIPCHK(ipcr::launch_gather(s->stream, g->planes, g->rst, dsegs, (uint32_t)n, s->d_amps));
     // the amplicons become the records of a private genome on this scratch's stream: no waits between the packs
     if (!s->nest || s->nest->cap_cols < cols + 64 || s->nest->max_records < n) {
-        if (s->nest) ipcr_genome_destroy(s->nest);
-        s->nest = nullptr;
-        st = ipcr_genome_create_on((cols + (cols >> 2) + 64) * IPCR_COLUMN_BASES, (uint32_t)std::max<size_t>(n + (n >> 2), 16), s->device, &s->nest);
+        st = scratch_private_genome(s, &s->nest, (cols + (cols >> 2) + 64) * IPCR_COLUMN_BASES, (uint32_t)std::max<size_t>(n + (n >> 2), 16));
         if (st != IPCR_OK) return st;
-        s->nest->exc_capture = false;
-        (void)hipStreamDestroy(s->nest->stream);
-        s->nest->stream = s->stream;
-        s->nest->shared_stream = true;
     }
     genome_clear(s->nest);
     {   // one pack launch for all amplicons; its record table goes behind the segment table in the same device buffer
@@ -4255,9 +4295,7 @@ static ipcr_status nested_run(const ipcr_genome *g, const ipcr_window *windows, 
     }
     st = scan_hits(inner, s, s->nest);
     if (st != IPCR_OK) return st;
-    std::vector<uint8_t> fl(n);
-    const bool any = genome_any_reset(s->nest);
-    for (size_t r = 0; r < n; ++r) fl[r] = (uint8_t)((s->nest->flags[r] & 1u) | (any ? 2u : 0u));
+    const std::vector<uint8_t> fl = genome_record_flags(s->nest); // (one record per amplicon)
     st = join_sorted_hits(inner, s, s->nest->rec_len.data(), fl.data(), (uint32_t)n, nullptr, nullptr);
     if (st != IPCR_OK) return st;
     // best inner product per amplicon: fewest total mismatches, longest, leftmost, end, pair ID (nested.go:35-51);
@@ -4286,36 +4324,13 @@ ipcr_status ipcr_nested_windows(const ipcr_genome *g, const ipcr_window *windows
     return nested_run(g, windows, n, inner, s, out);
 }
 
-// the products of the last scan on `outer` as windows of the genome their amplicons lie in
-static std::vector<ipcr_window> outer_windows(const ipcr_scratch *outer, bool in_windows) {
-    const size_t n = outer->products.size();
-    std::vector<ipcr_window> w(n);
-    for (size_t i = 0; i < n; ++i) {
-        const ipcr_product &pr = outer->products[i];
-        w[i].start = pr.start;
-        w[i].end = pr.end;
-        w[i].record = pr.record;
-        w[i].reserved = 0;
-        // products of ipcr_scan_genome_chunked: `record` is a window, coordinates are window-local (as probe_begin puts them back)
-        if (in_windows && pr.record >= 0 && (size_t)pr.record < outer->windows.size()) {
-            const ipcr_chunk_window &cw = outer->windows[(size_t)pr.record];
-            w[i].record = (int32_t)cw.record;
-            w[i].start += (int64_t)cw.start;
-            w[i].end += (int64_t)cw.start;
-        } else if (in_windows) {
-            w[i].record = -1; // (nested_run refuses it: record outside the genome)
-        }
-    }
-    return w;
-}
-
 ipcr_status ipcr_nested_products(const ipcr_scratch *outer, const ipcr_genome *g, const ipcr_panel *inner,
                                  ipcr_scratch *s, ipcr_nested_hit *out, int64_t n_out) {
     if (!outer) return fail(IPCR_ERR_INVALID, "ipcr_nested_products: null argument");
     if (outer == s) return fail(IPCR_ERR_INVALID, "ipcr_nested_products: the inner scan needs a scratch of its own");
     const size_t n = outer->products.size();
     if ((int64_t)n != n_out) return fail(IPCR_ERR_INVALID, "n_out (%lld) != products of the last scan (%zu)", (long long)n_out, n);
-    const std::vector<ipcr_window> w = outer_windows(outer, outer->products_in_windows);
+    const std::vector<ipcr_window> w = product_windows(outer, outer->products_in_windows);
     return nested_run(g, w.data(), (int64_t)n, inner, s, out);
 }
 
@@ -4330,7 +4345,7 @@ ipcr_status ipcr_product_sites(const ipcr_scratch *s, const ipcr_genome *g, uint
     if ((int64_t)n != n_products) return fail(IPCR_ERR_INVALID, "ipcr_product_sites: n_products (%lld) != products of the last scan (%zu)", (long long)n_products, n);
     if (n && s->last_was_chunk)
         return fail(IPCR_ERR_INVALID, "ipcr_product_sites: the last scan was an ipcr_scan_chunk, whose caller holds the chunk's bytes");
-    const std::vector<ipcr_window> w = outer_windows(s, s->products_in_windows);
+    const std::vector<ipcr_window> w = product_windows(s, s->products_in_windows);
     std::vector<ipcr_site> sites(2 * n);
     for (size_t i = 0; i < n; ++i) {
         const ipcr_product &pr = s->products[i];
@@ -4379,17 +4394,16 @@ static ipcr_status thermo_run(const char *what, const ipcr_scratch *s, const ipc
     // product's left primer is the pair's reverse primer (engine.go:326-331).  An end is skipped when the amplicon is shorter
     // than its primer (score.go:1530, :1540).  A primer never spans the origin, so both windows lie whole in the record, also
     // for a wrap-around product.
-    const std::vector<ipcr_window> w = outer_windows(s, in_windows);
+    const std::vector<ipcr_window> w = product_windows(s, in_windows);
     std::vector<ipcr_thermo_end> ends(2 * n);
     for (size_t i = 0; i < n; ++i) {
         const ipcr_product &pr = s->products[i];
         if (pr.pair < 0 || (size_t)pr.pair >= npairs) return fail(IPCR_ERR_INVALID, "%s: product %zu: no pair %d", what, i, pr.pair);
-        if (w[i].record < 0 || (size_t)w[i].record >= g->rec_len.size()) return fail(IPCR_ERR_INVALID, "%s: product %zu: no record %d", what, i, w[i].record);
-        const int64_t L = (int64_t)g->rec_len[(size_t)w[i].record], a = w[i].start, b = w[i].end;
-        if (a < 0 || b < 0 || a > L || b > L)
-            return fail(IPCR_ERR_INVALID, "%s: product %zu [%lld, %lld) outside its record of %lld bases", what, i, (long long)a, (long long)b, (long long)L);
-        const int64_t amp = a <= b ? b - a : (L - a) + b;
-        const uint64_t R = g->rec_start[(size_t)w[i].record];
+        Span sp;
+        const ipcr_status ps = resolve_span(what, "product", i, g, w[i].record, w[i].start, w[i].end, &sp);
+        if (ps != IPCR_OK) return ps;
+        const int64_t L = (int64_t)sp.L, a = (int64_t)sp.a, b = (int64_t)sp.b, amp = (int64_t)sp.len();
+        const uint64_t R = sp.R;
         const uint32_t left = 2u * (uint32_t)pr.pair + (pr.type == 0 ? 0u : 1u), right = left ^ 1u;
         const int64_t ln = (int64_t)prim[left].len, rn = (int64_t)prim[right].len;
         ipcr_thermo_end &el = ends[2 * i], &er = ends[2 * i + 1];
@@ -4407,37 +4421,18 @@ static ipcr_status thermo_run(const char *what, const ipcr_scratch *s, const ipc
         }
     }
     DeviceGuard dg(g->device);
-    {   // padding and packing must be complete: waits on the host for the genome's own stream (a chunk genome's is its scratch's)
-        std::lock_guard<std::mutex> lk(g->read_mu);
-        const ipcr_status st = genome_finalize(g);
-        if (st != IPCR_OK) return st;
-    }
-    uint64_t piece = READ_PIECE_SITES; // products per launch
-    if (const char *e = getenv("IPCR_TEST_THERMO_PIECE"))
-        if (*e) piece = std::min<uint64_t>(piece, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
-    piece = std::min<uint64_t>(piece, n);
-    ReadCtx *c = nullptr;
-    ipcr_status st = read_ctx_acquire(g->device, &c);
+    ipcr_status st = genome_reader_ready(what, g, nullptr); // (a chunk genome's own stream is its scratch's)
     if (st != IPCR_OK) return st;
-    hipError_t e = hipSuccess;
-    if (c->ends_cap < piece) {
-        if (c->d_ends) (void)hipFree(c->d_ends);
-        if (c->h_ends) (void)hipHostFree(c->h_ends);
-        c->d_ends = c->h_ends = nullptr;
-        c->ends_cap = 0;
-        const uint64_t cap = std::min<uint64_t>(READ_PIECE_SITES, std::max<uint64_t>(piece + (piece >> 1), 4096));
-        e = hipMalloc((void **)&c->d_ends, cap * 2 * sizeof(ipcr_thermo_end));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_ends, cap * 2 * sizeof(ipcr_thermo_end), hipHostMallocDefault);
-        if (e == hipSuccess) c->ends_cap = cap;
-    }
-    if (e == hipSuccess && c->primers_cap < prim.size()) {
-        if (c->d_primers) (void)hipFree(c->d_primers);
-        c->d_primers = nullptr;
-        c->primers_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(prim.size() * 2, 64);
-        e = hipMalloc((void **)&c->d_primers, cap * sizeof(ipcr_thermo_primer));
-        if (e == hipSuccess) c->primers_cap = cap;
-    }
+    const uint64_t piece = std::min<uint64_t>(test_piece("IPCR_TEST_THERMO_PIECE", READ_PIECE_SITES), n); // products per launch
+    ReadCtx *c = nullptr;
+    st = read_ctx_acquire(g->device, &c);
+    if (st != IPCR_OK) return st;
+    const uint64_t end_bytes = 2 * sizeof(ipcr_thermo_end); // per product
+    const uint64_t ends_cap = std::min<uint64_t>(READ_PIECE_SITES, std::max<uint64_t>(piece + (piece >> 1), 4096)) * end_bytes;
+    hipError_t e = grow_device((void **)&c->d_ends, &c->d_ends_cap, piece * end_bytes, ends_cap);
+    if (e == hipSuccess) e = grow_pinned((void **)&c->h_ends, &c->h_ends_cap, piece * end_bytes, ends_cap);
+    if (e == hipSuccess)
+        e = grow_device((void **)&c->d_primers, &c->primers_cap, prim.size() * sizeof(ipcr_thermo_primer), std::max<uint64_t>(prim.size() * 2, 64) * sizeof(ipcr_thermo_primer));
     static_assert(READ_PIECE_SITES * sizeof(double) <= READ_PIECE_BYTES, "a piece's scores fit the context's output buffer");
     if (e == hipSuccess) e = hipMemcpyAsync(c->d_primers, prim.data(), prim.size() * sizeof(ipcr_thermo_primer), hipMemcpyHostToDevice, c->st);
     for (size_t i0 = 0; i0 < n && e == hipSuccess; i0 += piece) {
@@ -4487,7 +4482,7 @@ ipcr_status ipcr_nested_scratch_products(const ipcr_scratch *outer, const ipcr_p
     if (n == 0) return IPCR_OK; // (an empty chunk, or an empty panel's chunk scan, which packs nothing)
     if (!outer->chunk) return fail(IPCR_ERR_INVALID, "ipcr_nested_scratch_products: the outer scratch holds no chunk");
     if (outer->device != s->device) return fail(IPCR_ERR_INVALID, "ipcr_nested_scratch_products: scratches of different devices");
-    const std::vector<ipcr_window> w = outer_windows(outer, false);
+    const std::vector<ipcr_window> w = product_windows(outer, false);
     return nested_run(outer->chunk, w.data(), (int64_t)n, inner, s, out);
 }
 

@@ -321,6 +321,78 @@ def test_argument_errors_come_from_the_host_check(scanned):
     assert L.ipcr_thermo_legacy_scratch_products(sc._h, None, 0, out, len(ps)) == _lib.OK
 
 
+def test_every_product_consumer_translates_and_refuses_alike():
+    """The probe rescan, the nested scan, the site read and the thermo score of a chunked scan's window-local products equal
+    those of the whole-record scan, product for product in record coordinates; against a genome whose records end before
+    the products do, all four refuse with IPCR_ERR_INVALID (a probe `end` after the refused `begin` too), and the same
+    scratch then serves the right genome."""
+    from ipcr_amd import _lib, engine, nested, primer
+    rng = random.Random(21)
+    F, Rv, IF, IR, probe = rnd(rng, 20), rnd(rng, 22), rnd(rng, 18), rnd(rng, 18), rnd(rng, 16)
+
+    def amp(mm_f, mm_r, with_probe):                                    # outer sites, the inner pair inside, the probe between
+        return (mutate(F, mm_f) + rnd(rng, 15) + IF + rnd(rng, 20) + (probe if with_probe else rnd(rng, 16)) + rnd(rng, 30)
+                + rc(IR) + rnd(rng, 15) + rc(mutate(Rv, mm_r)))
+    recs = [bytearray(rnd(rng, 6200).encode()), bytearray(rnd(rng, 6100).encode())]
+    # windows of 4000 every 3000: [0, 4000) and [3000, end).  500: the first window only (and inside a 2 kb record);
+    # 3300: both windows; 5200 and record 1's 4500: the second window only, whose start is not 0
+    plan = [(0, 500, (), (), True), (0, 3300, (1,), (), True), (0, 5200, (), (20,), False), (1, 4500, (3, 17), (2,), True)]
+    for r, pos, mm_f, mm_r, with_probe in plan:
+        a = amp(mm_f, mm_r, with_probe).encode()
+        recs[r][pos:pos + len(a)] = a
+    recs = [bytes(r) for r in recs]
+    oeng = engine.New(engine.Config(MaxMM=2, TerminalWindow=0, MinLen=0, MaxLen=400, SeedLen=12))
+    ieng = engine.New(engine.Config(MaxMM=1, TerminalWindow=0, SeedLen=12))
+    cpo, cpi = oeng.CompilePanel([primer.Pair("outer", F, Rv)]), ieng.CompilePanel([primer.Pair("inner", IF, IR)])
+    sco, scc, sci = oeng.NewSimulationScratch(cpo), oeng.NewSimulationScratch(cpo), ieng.NewSimulationScratch(cpi)
+    g, small = new_genome(recs), new_genome([r[:2000] for r in recs])
+    for i, s in enumerate(recs):
+        g.add_record("r%d" % i, s)
+        small.add_record("s%d" % i, s[:2000])
+
+    def consumers(sc, prods):
+        """per product: (probe hit, inner product, sites, score bits)"""
+        hits = [(h.found, h.strand, h.pos, h.mm) for h in sc.probe_products(probe, 1, g)]
+        inner = [(n.InnerFound, n.InnerPairID, n.InnerStart, n.InnerEnd, n.InnerLength, n.InnerType, n.InnerFwdMM, n.InnerRevMM)
+                 for n in nested.NestedProducts(sc, prods, g, cpi, sci)]
+        return list(zip(hits, inner, sc.product_sites(g), [bits(x) for x in sc.thermo_scores(g)]))
+
+    whole = oeng.ScanGenome(g, cpo, sco)
+    assert sorted((p.Record, p.Start) for p in whole) == sorted(c[:2] for c in plan)
+    want = {(p.Record, p.Start, p.End, p.Type): c for p, c in zip(whole, consumers(sco, whole))}
+    assert sum(c[0][0] for c in want.values()) == 3 and all(c[1][0] for c in want.values())   # the probe and the inner pair are found
+    assert len({c[3] for c in want.values()}) == len(plan)             # ... and the products score differently
+    for (r, a, b, _), c in want.items():
+        assert c[2] == (recs[r][a:a + len(F)].decode(), rc(recs[r][b - len(Rv):b].decode()))
+    chunked = oeng.ScanGenomeChunked(g, cpo, scc, 4000, 1000)
+    wins = scc.chunk_windows()
+    assert len(chunked) == len(whole) + 1 and sum(wins[p.Record].start > 0 for p in chunked) == 3
+    got = consumers(scc, chunked)
+    for p, c in zip(chunked, got):
+        w = wins[p.Record]
+        k = (w.record, w.start + p.Start, w.start + p.End, p.Type)
+        assert c == want[k], (k, c, want[k])
+    # the refusal: the first product fits the short records, the others end behind them
+    L = _lib.lib()
+    for sc, prods, was in ((sco, whole, list(want.values())), (scc, chunked, got)):
+        n = len(prods)
+        ph, nh, sc_out = (_lib.ProbeHit * n)(), (_lib.NestedHit * n)(), (C.c_double * n)()
+        offs, need, buf = (C.c_uint64 * (2 * n + 1))(), C.c_uint64(), C.create_string_buffer(2 * n * _lib.IPCR_MAX_PRIMER_LEN)
+
+        def calls(genome):
+            return [L.ipcr_probe_products_begin(sc._h, genome._h, probe.encode(), 1),
+                    L.ipcr_probe_products_end(sc._h, ph, n),
+                    L.ipcr_nested_products(sc._h, genome._h, cpi._h, sci._h, nh, n),
+                    L.ipcr_product_sites(sc._h, genome._h, buf, len(buf), offs, n, C.byref(need)),
+                    L.ipcr_thermo_legacy_products(sc._h, genome._h, None, 0, sc_out, n)]
+        assert calls(small) == [_lib.ERR_INVALID] * 5
+        assert calls(g) == [_lib.OK] * 5
+        assert [((h.found, h.strand, h.pos, h.mm), bits(x)) for h, x in zip(ph, sc_out)] == [(c[0], c[3]) for c in was]
+        assert [bool(h.found) for h in nh] == [c[1][0] for c in was]
+    g.close()
+    small.close()
+
+
 # ---------------------------------------------------------------- the driver
 
 def run_cli(argv, env=None, monkeypatch=None):

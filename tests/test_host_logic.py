@@ -867,7 +867,8 @@ def test_plain_staging_allocations_clear_the_fine_grained_flag():
     """A genome's staging buffer is fine-grained (hipExtMallocWithFlags) when the host packer writes it through the PCIe BAR, and
     staging_fine says so; the ASCII paths (ipcr_genome_add_record, ipcr_scan_chunk) re-allocate it with plain hipMalloc.  Such a
     re-allocation must clear staging_fine between the hipFree of the old buffer and the hipMalloc of the new one: otherwise the next
-    host-packed record (4096 bases, then 4090, then 4096 again) writes its planes through the BAR into coarse-grained memory."""
+    host-packed record (4096 bases, then 4090, then 4096 again) writes its planes through the BAR into coarse-grained memory.
+    Every path grows the buffer through genome_staging, so the library allocates g->staging in that ONE place, of either kind."""
     import glob
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     seen = 0
@@ -883,7 +884,10 @@ def test_plain_staging_allocations_clear_the_fine_grained_flag():
             between = "\n".join(lines[free:i])
             assert re.search(r"g->staging_fine\s*=\s*false\s*;", between), \
                 "%s: plain hipMalloc of g->staging leaves staging_fine as it was" % where
-    assert seen >= 3
+            assert "hipExtMallocWithFlags((void **)&g->staging" in line, "%s: the fine-grained allocation lives elsewhere" % where
+    assert seen == 1
+    text = "".join(open(p).read() for p in glob.glob(os.path.join(root, "ipcr_amd", "csrc", "*.cpp")))
+    assert len(re.findall(r"Malloc\w*\s*\(\s*\(void\s*\*\*\)\s*&\s*g->staging\b", text)) == 2   # ... and nowhere else
 
 
 def _brute_matches(seq, pat, k, left, tw_dev):
