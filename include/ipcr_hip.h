@@ -511,7 +511,8 @@ ipcr_status ipcr_nested_scratch_products(const ipcr_scratch *outer, const ipcr_p
  * reversed (score.go:1539-1547, restated as it is).  An end adds nothing when its primer is not pure ACGT or the amplicon is
  * shorter than the primer; two perfect ends score -0.0.  The penalty of an end is ipcr_thermo_legacy_penalty below; --allow-indel
  * cannot change it (a primer and a window of equal length: the gap state of the reference's DP never reaches its last cell).
- * The NN models (nn-duplex-v1, nn-structure-v1) and --single-stranded are not built.
+ * Of the NN models nn-duplex-v1 is built as a library call (ipcr_thermo_nn_duplex_products below); nn-structure-v1 and
+ * --single-stranded are not built.
  *
  * ipcr_thermo_legacy_products: every product of the last scan on `s` over the resident genome `g`, scored on the device: one
  * kernel reads the two windows of a product from the tiles and writes one double (out[i] <-> product i); one launch per 2^21
@@ -544,6 +545,61 @@ ipcr_status ipcr_thermo_legacy_penalty(const char *primer5to3, const char *targe
  * context heuristic: 1.0, less 0.05 when the four flanks hold at least two more G/C than A/T.  Upper case only, as the
  * reference; IPCR_ERR_INVALID where its look-up returns ok == false (p outside ACGT, t outside ACGTN). */
 ipcr_status ipcr_thermo_mismatch_ddg(char p5, char p, char p3, char t5, char t, char t3, double *out);
+
+/* ---- ipcr-thermo, --thermo-model nn-duplex-v1: Score.scoreNNDuplexComponents -- internal/thermovisitors/score.go:594-690,
+ * core/thermo/imperfect.go:248-436 ----
+ * Score = the smaller of the two ends' anneal margins (the left one on a tie), margin = tm_c of the end - anneal_c.  An end is the
+ * primer's own perfect duplex -- its Tm and its denominator D = |EffectiveDenomCalK| depend on the primer and the solution
+ * only, so the caller computes them once per panel (`base`, below) -- less a mismatch penalty, plus a dangling-end term:
+ *   penalty = the sum, left to right over the columns i whose pair is not Watson-Crick, of max(raw * mult + term, 0), clamped at 0;
+ *             raw = ddG * 1000 / D with ddG = ipcr_thermo_mismatch_ddg, flanks N outside the window; mult = 2.0 for i >= n - 3, else
+ *             1.5 for i < 3, else 1.0; term = 1.5 at i == n - 1, else 0.5 at i == 0, else 0.0
+ *   dangling_adjustment = -(g * 1000) / D when the template base next to the primer's 3' end exists, is A/C/G/T and the primer's
+ *             last column is a Watson-Crick pair, else 0; g = the 5'-dangling dG37 of SantaLucia & Hicks 2004, table 3, by
+ *             (dangling base, template base of the last column).  The primer's 5' side gets no term (the reference passes none).
+ *   tm_c = (base tm_c - penalty) + dangling_adjustment
+ * Left end: the product's left primer (a revcomp product's is the pair's reverse primer) on the base-by-base complement of the
+ * first n bases of the amplicon; its dangling base is the complement of amplicon[n], present when the amplicon is longer than
+ * n.  Right end: its right primer on the LAST n bases of the amplicon reversed and not complemented; its dangling base is
+ * amplicon[len - n - 1] as it is.  On a circular product across the origin that neighbour may lie on the other side of the record.
+ * A product whose left or right primer is not pure ACGT, or whose amplicon is shorter than either primer, is not scorable (the
+ * reference returns an error): its score is NaN, the end at fault carries status 1 or 2 and tm_c = NaN, and the call returns IPCR_OK.
+ * The one deviation from the reference: a site byte outside ACGT reads as N, where the reference errors on one outside ACGTN; on
+ * the device a base is A/C/G/T where the tiles hold an upper-case A/C/G/T and N otherwise.
+ * Out of scope: --score-profile, the IUPAC expansion policies, --allow-indel and --single-stranded under NN, DeltaGAtAnnealKcal,
+ * nn-structure-v1, and the drivers (python -m ipcr_amd.thermo_cli refuses the model).
+ *
+ * base[2 p] / base[2 p + 1]: thermo.PerfectDuplex of pair p's forward / reverse primer on its own complement: tm_c = TmC, denom =
+ * |EffectiveDenomCalK| (200.0 when that is NaN, +-Inf or 0).  n_base must be twice the panel's pair count.
+ * ipcr_thermo_nn_duplex_products: every product of the last scan on `s` over the resident genome `g`, scored on the device: one
+ * kernel reads the two windows and the two dangling bases of a product from the tiles and writes one double (score[i] <-> product
+ * i) and, with `ends` (may be NULL), ends[2 i] / ends[2 i + 1], its left / right end.  It shares its body with
+ * ipcr_thermo_legacy_products: one launch per 2^21 products, window-local products of ipcr_scan_genome_chunked are put back first,
+ * and the device result equals ipcr_thermo_nn_duplex_end's bit for bit.  Every pair, record, window, dangling position and
+ * count is checked on the host before anything is launched: IPCR_ERR_INVALID as for ipcr_thermo_legacy_products, and when
+ * n_base is not twice the pair count, a base entry's denom is not finite and > 0, its tm_c or anneal_c is not finite.
+ * ipcr_thermo_nn_duplex_scratch_products: the same for the products of the LAST ipcr_scan_chunk on `s`. */
+typedef struct ipcr_thermo_nn_primer {
+    double tm_c;            /* PerfectDuplex: TmC */
+    double denom;           /* |EffectiveDenomCalK|, cal/K/mol */
+} ipcr_thermo_nn_primer;
+typedef struct ipcr_thermo_nn_end {
+    double tm_c, mismatch_penalty_c, dangling_adjustment_c;
+    uint32_t mismatch_count;
+    uint16_t n_count;       /* window bases that read N */
+    uint16_t status;        /* 0 scored; 1 primer not pure ACGT; 2 amplicon shorter than this primer */
+} ipcr_thermo_nn_end;       /* 32 bytes */
+ipcr_status ipcr_thermo_nn_duplex_products(const ipcr_scratch *s, const ipcr_genome *g, const ipcr_thermo_nn_primer *base,
+                                           int64_t n_base, double anneal_c, double *score, ipcr_thermo_nn_end *ends,
+                                           int64_t n_products);
+ipcr_status ipcr_thermo_nn_duplex_scratch_products(const ipcr_scratch *s, const ipcr_thermo_nn_primer *base, int64_t n_base,
+                                                   double anneal_c, double *score, ipcr_thermo_nn_end *ends, int64_t n_products);
+/* host only, no device: one end, as above, for a primer (5'->3') on a target given 3'->5' of the SAME length (1 ..
+ * IPCR_MAX_PRIMER_LEN); dangling3p: the template base next to the primer's 3' end, 0 for none.  Case is folded.  A primer byte
+ * outside ACGT: status 1, tm_c = NaN, IPCR_OK.  A target or dangling byte outside ACGT reads as N (the deviation above).
+ * IPCR_ERR_INVALID for unequal lengths, an empty or too long primer, denom not finite and > 0, or tm_c not finite. */
+ipcr_status ipcr_thermo_nn_duplex_end(const char *primer5to3, const char *target3to5, char dangling3p, double tm_c, double denom,
+                                      ipcr_thermo_nn_end *out);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,18 @@ class NestedHit(C.Structure):
                 ("length", C.c_int64)]
 
 
+class ThermoNNPrimer(C.Structure):
+    """ipcr_thermo_nn_primer: TmC and |EffectiveDenomCalK| of a primer's own perfect duplex"""
+    _fields_ = [("tm_c", C.c_double), ("denom", C.c_double)]
+
+
+class ThermoNNEnd(C.Structure):
+    """ipcr_thermo_nn_end: one end of a product under nn-duplex-v1 (status 0 scored, 1 primer not pure ACGT, 2 amplicon
+    shorter than the primer)"""
+    _fields_ = [("tm_c", C.c_double), ("mismatch_penalty_c", C.c_double), ("dangling_adjustment_c", C.c_double),
+                ("mismatch_count", C.c_uint32), ("n_count", C.c_uint16), ("status", C.c_uint16)]
+
+
 class ScanStats(C.Structure):
     _fields_ = [("pack_ms", C.c_double), ("filter_ms", C.c_double), ("verify_ms", C.c_double),
                 ("total_ms", C.c_double), ("bases", C.c_uint64), ("tile_bytes", C.c_uint64),
@@ -184,6 +196,11 @@ SYMBOLS = {
     "ipcr_thermo_legacy_scratch_products": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.c_int64]),
     "ipcr_thermo_legacy_penalty": (C.c_int, [C.c_char_p, C.c_char_p, C.c_double, C.POINTER(C.c_double)]),
     "ipcr_thermo_mismatch_ddg": (C.c_int, [C.c_char, C.c_char, C.c_char, C.c_char, C.c_char, C.c_char, C.POINTER(C.c_double)]),
+    "ipcr_thermo_nn_duplex_products": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ThermoNNPrimer), C.c_int64, C.c_double,
+                                                 C.POINTER(C.c_double), C.POINTER(ThermoNNEnd), C.c_int64]),
+    "ipcr_thermo_nn_duplex_scratch_products": (C.c_int, [C.c_void_p, C.POINTER(ThermoNNPrimer), C.c_int64, C.c_double,
+                                                         C.POINTER(C.c_double), C.POINTER(ThermoNNEnd), C.c_int64]),
+    "ipcr_thermo_nn_duplex_end": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char, C.c_double, C.c_double, C.POINTER(ThermoNNEnd)]),
 }
 
 _lib = None

@@ -71,6 +71,25 @@ struct ipcr_thermo_end {
     uint32_t primer, n;
 };
 
+// nn-duplex-v1 thermo score (thermo_nn_kernels.hip).  A primer of the panel as codes with the Tm and the denominator D of its
+// own perfect duplex; len == 0: the primer is not pure ACGT.  Entry 2 p is pair p's forward primer, 2 p + 1 its reverse primer.
+struct ipcr_thermo_nn_primer_dev {
+    double tm, denom;
+    uint32_t len, reserved;
+    uint8_t code[128];
+};
+// one end of a product: primer base i lies on the base at padded position P + i (left end) or P - i (right end:
+// IPCR_THERMO_NN_BACK), complemented under IPCR_THERMO_NN_COMP; D: the padded position of the dangling base, read under the
+// same transform, or IPCR_THERMO_NN_NO_DANGLING.  The host resolves D: on a circular product across the origin it lies on the
+// other side of the record.  n == 0: the end is not scored and `flags >> 8` is its status (ipcr_thermo_nn_end.status).
+#define IPCR_THERMO_NN_BACK 1u
+#define IPCR_THERMO_NN_COMP 2u
+#define IPCR_THERMO_NN_NO_DANGLING (~0ull)
+struct ipcr_thermo_nn_end_dev {
+    uint64_t P, D;
+    uint32_t primer, n, flags, reserved;
+};
+
 struct ipcr_probe_rec { // layout-identical to ipcr_probe_hit
     int32_t found, strand, pos, mm;
 };

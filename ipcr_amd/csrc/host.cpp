@@ -1860,9 +1860,10 @@ struct ReadCtx {
     uint64_t d_sites_cap = 0, h_sites_cap = 0, d_bad_cap = 0, h_bad_cap = 0; // in bytes, as every capacity here
     // thermo_run (grown by its calls on this context, never shrunk): the ends of one piece, and the panel's primer table;
     // the scores of a piece land in d_out
-    ipcr_thermo_end *d_ends = nullptr, *h_ends = nullptr; // h_ends pinned
+    // (ipcr_thermo_end / ipcr_thermo_primer, or their nn-duplex-v1 forms: the call that runs knows which)
+    void *d_ends = nullptr, *h_ends = nullptr; // h_ends pinned
     uint64_t d_ends_cap = 0, h_ends_cap = 0;
-    ipcr_thermo_primer *d_primers = nullptr;
+    void *d_primers = nullptr;
     uint64_t primers_cap = 0;
 };
 std::mutex g_read_mu;
@@ -4358,44 +4359,70 @@ ipcr_status ipcr_product_sites(const ipcr_scratch *s, const ipcr_genome *g, uint
     return read_sites("ipcr_product_sites", const_cast<ipcr_genome *>(g), sites.data(), (int64_t)(2 * n), out, cap, offsets, needed);
 }
 
-// ------------------------------------------------------------------------------ thermo: legacy-heuristic score
+// ------------------------------------------------------------------------------ thermo: the per-product scores
 
-// The one body of ipcr_thermo_legacy_products / ipcr_thermo_legacy_scratch_products (`what` names the caller in messages):
-// Score of every product of the last scan on `s` (internal/thermovisitors/score.go:1522-1552), the two primer-length windows
-// read from the tiles of `g` -- the resident genome, or the scratch's private chunk genome -- on the device.  Everything is
-// checked here, before anything is launched: the kernel trusts its descriptors.
+// what an nn-duplex-v1 caller adds to thermo_run's arguments (null there: the legacy-heuristic score)
+struct ThermoNN {
+    const ipcr_thermo_nn_primer *base; // entry 2 p / 2 p + 1: pair p's forward / reverse primer
+    int64_t n_base;
+    double anneal_c;
+    ipcr_thermo_nn_end *ends; // may be null
+};
+
+// The one body of ipcr_thermo_legacy_products / ipcr_thermo_legacy_scratch_products and of their nn-duplex-v1 forms (`what`
+// names the caller in messages): Score of every product of the last scan on `s` (internal/thermovisitors/score.go:1522-1552,
+// :637-690), the two primer-length windows -- and under nn-duplex-v1 the base next to each -- read from the tiles of `g`, the
+// resident genome or the scratch's private chunk genome, on the device.  Everything is checked here, before anything is
+// launched: the kernels trust their descriptors.
 static ipcr_status thermo_run(const char *what, const ipcr_scratch *s, const ipcr_genome *cg, bool in_windows, const double *denom,
-                              int64_t n_denom, double *out, int64_t n_products) {
+                              int64_t n_denom, const ThermoNN *nn, double *out, int64_t n_products) {
     const ipcr_panel *p = s->panel;
     const size_t n = s->products.size(), npairs = p->fwd.size();
     if ((int64_t)n != n_products) return fail(IPCR_ERR_INVALID, "%s: n_products (%lld) != products of the last scan (%zu)", what, (long long)n_products, n);
-    if (n_denom != 0 && (n_denom != (int64_t)(2 * npairs) || !denom))
+    if (!nn && n_denom != 0 && (n_denom != (int64_t)(2 * npairs) || !denom))
         return fail(IPCR_ERR_INVALID, "%s: n_denom (%lld) must be 0 or twice the panel's pair count (%zu), with a table", what, (long long)n_denom, npairs);
     if (n && !out) return fail(IPCR_ERR_INVALID, "%s: null output", what);
     { const ipcr_status ds = same_device(s, cg); if (ds != IPCR_OK) return ds; }
     if (n == 0) return IPCR_OK;
     ipcr_genome *g = const_cast<ipcr_genome *>(cg);
     // the primers: entry 2 p = pair p's forward primer, 2 p + 1 its reverse primer; a primer that is not pure ACGT has
-    // length 0 here and its end adds nothing (toUpperACGT, score.go:239-251: panel primers are upper case already)
-    std::vector<ipcr_thermo_primer> prim(2 * npairs);
+    // length 0 here: under the legacy model its end adds nothing (toUpperACGT, score.go:239-251: panel primers are upper
+    // case already), under nn-duplex-v1 its products are not scorable (score.go:638-642)
+    std::vector<ipcr_thermo_primer> prim(nn ? 0 : 2 * npairs);
+    std::vector<ipcr_thermo_nn_primer_dev> nprim(nn ? 2 * npairs : 0);
+    std::vector<uint32_t> plen(2 * npairs);
     for (size_t k = 0; k < 2 * npairs; ++k) {
         const std::string &seq = (k & 1) ? p->rev[k >> 1] : p->fwd[k >> 1];
-        ipcr_thermo_primer &t = prim[k];
-        memset(&t, 0, sizeof t);
-        t.denom = n_denom ? denom[k] : IPCR_THERMO_FIXED_DENOM;
+        uint8_t *code = nullptr;
+        if (nn) {
+            ipcr_thermo_nn_primer_dev &t = nprim[k];
+            memset(&t, 0, sizeof t);
+            t.tm = nn->base[k].tm_c;
+            t.denom = nn->base[k].denom;
+            code = t.code;
+        } else {
+            ipcr_thermo_primer &t = prim[k];
+            memset(&t, 0, sizeof t);
+            t.denom = n_denom ? denom[k] : IPCR_THERMO_FIXED_DENOM;
+            code = t.code;
+        }
         bool pure = !seq.empty() && seq.size() <= IPCR_MAX_PRIMER_LEN;
         for (size_t j = 0; j < seq.size() && pure; ++j) {
             const uint32_t c = ipcr_thermo_code((uint8_t)seq[j]);
-            if (c >= 4u) pure = false; else t.code[j] = (uint8_t)c;
+            if (c >= 4u) pure = false; else code[j] = (uint8_t)c;
         }
-        t.len = pure ? (uint32_t)seq.size() : 0u;
+        plen[k] = pure ? (uint32_t)seq.size() : 0u;
+        if (nn) nprim[k].len = plen[k]; else prim[k].len = plen[k];
     }
     // the ends: left = the first |left primer| bases of the amplicon, right = its last |right primer| bases; a revcomp
     // product's left primer is the pair's reverse primer (engine.go:326-331).  An end is skipped when the amplicon is shorter
-    // than its primer (score.go:1530, :1540).  A primer never spans the origin, so both windows lie whole in the record, also
-    // for a wrap-around product.
+    // than its primer (score.go:1530, :1540; :643-645).  A primer never spans the origin, so both windows lie whole in the
+    // record, also for a wrap-around product.  nn-duplex-v1 walks the right window backwards and not complemented
+    // (score.go:656-657) and reads the amplicon's base next to each window (:660-672): amplicon[ln] and amplicon[amp - rn - 1],
+    // which on a wrap-around product may lie on the other side of the origin -- resolved and checked here, one by one.
     const std::vector<ipcr_window> w = product_windows(s, in_windows);
-    std::vector<ipcr_thermo_end> ends(2 * n);
+    std::vector<ipcr_thermo_end> ends(nn ? 0 : 2 * n);
+    std::vector<ipcr_thermo_nn_end_dev> nends(nn ? 2 * n : 0);
     for (size_t i = 0; i < n; ++i) {
         const ipcr_product &pr = s->products[i];
         if (pr.pair < 0 || (size_t)pr.pair >= npairs) return fail(IPCR_ERR_INVALID, "%s: product %zu: no pair %d", what, i, pr.pair);
@@ -4405,43 +4432,86 @@ static ipcr_status thermo_run(const char *what, const ipcr_scratch *s, const ipc
         const int64_t L = (int64_t)sp.L, a = (int64_t)sp.a, b = (int64_t)sp.b, amp = (int64_t)sp.len();
         const uint64_t R = sp.R;
         const uint32_t left = 2u * (uint32_t)pr.pair + (pr.type == 0 ? 0u : 1u), right = left ^ 1u;
-        const int64_t ln = (int64_t)prim[left].len, rn = (int64_t)prim[right].len;
-        ipcr_thermo_end &el = ends[2 * i], &er = ends[2 * i + 1];
-        el = ipcr_thermo_end{0, left, 0};
-        er = ipcr_thermo_end{0, right, 0};
-        if (ln && amp >= ln) {
-            if (ln > L - a) return fail(IPCR_ERR_INVALID, "%s: product %zu: the %lld bases under its left primer at %lld leave its record of %lld bases", what, i, (long long)ln, (long long)a, (long long)L);
+        const int64_t ln = (int64_t)plen[left], rn = (int64_t)plen[right];
+        const bool lon = ln && amp >= ln, ron = rn && amp >= rn;
+        if (lon && ln > L - a) return fail(IPCR_ERR_INVALID, "%s: product %zu: the %lld bases under its left primer at %lld leave its record of %lld bases", what, i, (long long)ln, (long long)a, (long long)L);
+        if (ron && rn > b) return fail(IPCR_ERR_INVALID, "%s: product %zu: the %lld bases under its right primer end at %lld, before its record begins", what, i, (long long)rn, (long long)b);
+        if (!nn) {
+            ipcr_thermo_end &el = ends[2 * i], &er = ends[2 * i + 1];
+            el = ipcr_thermo_end{0, left, 0};
+            er = ipcr_thermo_end{0, right, 0};
+            if (lon) { el.P = R + (uint64_t)a; el.n = (uint32_t)ln; }
+            if (ron) { er.P = R + (uint64_t)(b - rn); er.n = (uint32_t)rn; }
+            continue;
+        }
+        // the record position of amplicon[k], k < amp, into *pos; false when it leaves the record (or, on a product that does
+        // not wrap, the amplicon): never for a span resolve_span passed, and checked all the same -- the kernel reads it as given
+        auto amp_pos = [&](int64_t k, int64_t *pos) {
+            int64_t q = a + k;
+            if (a > b && q >= L) q -= L;
+            *pos = q;
+            return k >= 0 && k < amp && q >= 0 && q < L && (a > b ? (q >= a || q < b) : (q >= a && q < b));
+        };
+        ipcr_thermo_nn_end_dev &el = nends[2 * i], &er = nends[2 * i + 1];
+        el = ipcr_thermo_nn_end_dev{0, IPCR_THERMO_NN_NO_DANGLING, left, 0, (ln ? 2u : 1u) << 8, 0};
+        er = ipcr_thermo_nn_end_dev{0, IPCR_THERMO_NN_NO_DANGLING, right, 0, (rn ? 2u : 1u) << 8, 0};
+        int64_t q = 0;
+        if (lon) {
             el.P = R + (uint64_t)a;
             el.n = (uint32_t)ln;
+            el.flags = IPCR_THERMO_NN_COMP;
+            if (amp > ln) {
+                if (!amp_pos(ln, &q)) return fail(IPCR_ERR_INVALID, "%s: product %zu: the base behind its left primer's window, at %lld, leaves its record of %lld bases", what, i, (long long)q, (long long)L);
+                el.D = R + (uint64_t)q;
+            }
         }
-        if (rn && amp >= rn) {
-            if (rn > b) return fail(IPCR_ERR_INVALID, "%s: product %zu: the %lld bases under its right primer end at %lld, before its record begins", what, i, (long long)rn, (long long)b);
-            er.P = R + (uint64_t)(b - rn);
+        if (ron) {
+            er.P = R + (uint64_t)(b - 1); // (rn >= 1 and rn <= b: b >= 1)
             er.n = (uint32_t)rn;
+            er.flags = IPCR_THERMO_NN_BACK;
+            if (amp > rn) {
+                if (!amp_pos(amp - rn - 1, &q)) return fail(IPCR_ERR_INVALID, "%s: product %zu: the base before its right primer's window, at %lld, leaves its record of %lld bases", what, i, (long long)q, (long long)L);
+                er.D = R + (uint64_t)q;
+            }
         }
     }
     DeviceGuard dg(g->device);
     ipcr_status st = genome_reader_ready(what, g, nullptr); // (a chunk genome's own stream is its scratch's)
     if (st != IPCR_OK) return st;
-    const uint64_t piece = std::min<uint64_t>(test_piece("IPCR_TEST_THERMO_PIECE", READ_PIECE_SITES), n); // products per launch
+    // per product: the two descriptors going in, the score -- and under nn-duplex-v1, when asked, the two ends -- coming out
+    const uint64_t end_bytes = 2 * (nn ? sizeof(ipcr_thermo_nn_end_dev) : sizeof(ipcr_thermo_end));
+    const uint64_t out_bytes = sizeof(double) + ((nn && nn->ends) ? 2 * sizeof(ipcr_thermo_nn_end) : 0);
+    const uint64_t piece_max = std::min<uint64_t>(READ_PIECE_SITES, READ_PIECE_BYTES / out_bytes); // a piece's output fits the context's buffer
+    const uint64_t piece = std::min<uint64_t>(test_piece("IPCR_TEST_THERMO_PIECE", piece_max), n); // products per launch
+    const void *ptab = nn ? (const void *)nprim.data() : (const void *)prim.data();
+    const uint64_t ptab_bytes = nn ? nprim.size() * sizeof(ipcr_thermo_nn_primer_dev) : prim.size() * sizeof(ipcr_thermo_primer);
+    const uint8_t *etab = nn ? (const uint8_t *)nends.data() : (const uint8_t *)ends.data();
     ReadCtx *c = nullptr;
     st = read_ctx_acquire(g->device, &c);
     if (st != IPCR_OK) return st;
-    const uint64_t end_bytes = 2 * sizeof(ipcr_thermo_end); // per product
     const uint64_t ends_cap = std::min<uint64_t>(READ_PIECE_SITES, std::max<uint64_t>(piece + (piece >> 1), 4096)) * end_bytes;
-    hipError_t e = grow_device((void **)&c->d_ends, &c->d_ends_cap, piece * end_bytes, ends_cap);
-    if (e == hipSuccess) e = grow_pinned((void **)&c->h_ends, &c->h_ends_cap, piece * end_bytes, ends_cap);
-    if (e == hipSuccess)
-        e = grow_device((void **)&c->d_primers, &c->primers_cap, prim.size() * sizeof(ipcr_thermo_primer), std::max<uint64_t>(prim.size() * 2, 64) * sizeof(ipcr_thermo_primer));
+    hipError_t e = grow_device(&c->d_ends, &c->d_ends_cap, piece * end_bytes, ends_cap);
+    if (e == hipSuccess) e = grow_pinned(&c->h_ends, &c->h_ends_cap, piece * end_bytes, ends_cap);
+    if (e == hipSuccess) e = grow_device(&c->d_primers, &c->primers_cap, ptab_bytes, std::max<uint64_t>(ptab_bytes * 2, 64 * sizeof(ipcr_thermo_nn_primer_dev)));
     static_assert(READ_PIECE_SITES * sizeof(double) <= READ_PIECE_BYTES, "a piece's scores fit the context's output buffer");
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_primers, prim.data(), prim.size() * sizeof(ipcr_thermo_primer), hipMemcpyHostToDevice, c->st);
+    static_assert(sizeof(ipcr_thermo_nn_end) == 32 && sizeof(ipcr_thermo_nn_end_dev) == 32, "the layouts the header and the kernel state");
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_primers, ptab, ptab_bytes, hipMemcpyHostToDevice, c->st);
+    double *d_score = reinterpret_cast<double *>(c->d_out);
+    ipcr_thermo_nn_end *d_ends_out = (nn && nn->ends) ? reinterpret_cast<ipcr_thermo_nn_end *>(c->d_out + piece * sizeof(double)) : nullptr;
     for (size_t i0 = 0; i0 < n && e == hipSuccess; i0 += piece) {
         const size_t m = std::min<size_t>(piece, n - i0);
-        memcpy(c->h_ends, ends.data() + 2 * i0, 2 * m * sizeof(ipcr_thermo_end));
-        e = hipMemcpyAsync(c->d_ends, c->h_ends, 2 * m * sizeof(ipcr_thermo_end), hipMemcpyHostToDevice, c->st);
-        if (e == hipSuccess) e = ipcr::launch_thermo_legacy(c->st, g->planes, c->d_ends, (uint32_t)m, c->d_primers, (uint32_t)prim.size(), reinterpret_cast<double *>(c->d_out));
-        if (e == hipSuccess) e = hipMemcpyAsync(out + i0, c->d_out, m * sizeof(double), hipMemcpyDeviceToHost, c->st);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->st); // (h_ends, d_out -- and `prim` -- are free for reuse after it)
+        memcpy(c->h_ends, etab + i0 * end_bytes, m * end_bytes);
+        e = hipMemcpyAsync(c->d_ends, c->h_ends, m * end_bytes, hipMemcpyHostToDevice, c->st);
+        if (e == hipSuccess && !nn)
+            e = ipcr::launch_thermo_legacy(c->st, g->planes, static_cast<const ipcr_thermo_end *>(c->d_ends), (uint32_t)m,
+                                           static_cast<const ipcr_thermo_primer *>(c->d_primers), (uint32_t)prim.size(), d_score);
+        if (e == hipSuccess && nn)
+            e = ipcr::launch_thermo_nn_duplex(c->st, g->planes, static_cast<const ipcr_thermo_nn_end_dev *>(c->d_ends), (uint32_t)m,
+                                              static_cast<const ipcr_thermo_nn_primer_dev *>(c->d_primers), (uint32_t)nprim.size(), nn->anneal_c,
+                                              d_score, d_ends_out);
+        if (e == hipSuccess) e = hipMemcpyAsync(out + i0, d_score, m * sizeof(double), hipMemcpyDeviceToHost, c->st);
+        if (e == hipSuccess && d_ends_out) e = hipMemcpyAsync(nn->ends + 2 * i0, d_ends_out, 2 * m * sizeof(ipcr_thermo_nn_end), hipMemcpyDeviceToHost, c->st);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->st); // (h_ends, d_out -- and the primer table -- are free for reuse after it)
     }
     if (e != hipSuccess) (void)hipStreamSynchronize(c->st);
     read_ctx_release(c);
@@ -4449,23 +4519,60 @@ static ipcr_status thermo_run(const char *what, const ipcr_scratch *s, const ipc
     return IPCR_OK;
 }
 
+// the per-primer base of an nn-duplex-v1 call against the scratch's panel: checked first, whatever else the call refuses
+static ipcr_status thermo_nn_check(const char *what, const ipcr_scratch *s, const ThermoNN *nn) {
+    const size_t npairs = s->panel->fwd.size();
+    if (nn->n_base != (int64_t)(2 * npairs) || (npairs && !nn->base))
+        return fail(IPCR_ERR_INVALID, "%s: n_base (%lld) must be twice the panel's pair count (%zu), with a table", what, (long long)nn->n_base, npairs);
+    for (size_t k = 0; k < 2 * npairs; ++k)
+        if (!std::isfinite(nn->base[k].tm_c) || !std::isfinite(nn->base[k].denom) || !(nn->base[k].denom > 0.0))
+            return fail(IPCR_ERR_INVALID, "%s: base entry %zu: tm_c (%g) must be finite and denom (%g) finite and > 0", what, k, nn->base[k].tm_c, nn->base[k].denom);
+    if (!std::isfinite(nn->anneal_c)) return fail(IPCR_ERR_INVALID, "%s: anneal_c (%g) must be finite", what, nn->anneal_c);
+    return IPCR_OK;
+}
+
+// the checks in front of thermo_run that the resident-genome and the scratch-chunk callers of either model share
+static ipcr_status thermo_products(const char *what, const ipcr_scratch *s, const ipcr_genome *g, const double *denom, int64_t n_denom,
+                                   const ThermoNN *nn, double *out, int64_t n_products) {
+    if (!s || !g) return fail(IPCR_ERR_INVALID, "%s: null argument", what);
+    if (nn) { const ipcr_status bs = thermo_nn_check(what, s, nn); if (bs != IPCR_OK) return bs; }
+    if (!s->products.empty() && s->last_was_chunk)
+        return fail(IPCR_ERR_INVALID, "%s: the last scan was an ipcr_scan_chunk: the _scratch_products form of this call scores its products", what);
+    return thermo_run(what, s, g, s->products_in_windows, denom, n_denom, nn, out, n_products);
+}
+
+static ipcr_status thermo_scratch_products(const char *what, const ipcr_scratch *s, const double *denom, int64_t n_denom, const ThermoNN *nn,
+                                           double *out, int64_t n_products) {
+    if (!s) return fail(IPCR_ERR_INVALID, "%s: null argument", what);
+    if (nn) { const ipcr_status bs = thermo_nn_check(what, s, nn); if (bs != IPCR_OK) return bs; }
+    if (!s->stream) return fail(IPCR_ERR_DEVICE, "host-only scratch: the thermo score has no CPU fallback");
+    if (!s->last_was_chunk) return fail(IPCR_ERR_INVALID, "%s: the scratch's last scan was not an ipcr_scan_chunk", what);
+    if (!s->chunk) { // (an empty chunk, or an empty panel's chunk scan, which packs nothing)
+        if (s->products.empty() && n_products == 0) return IPCR_OK;
+        return fail(IPCR_ERR_INVALID, "%s: the scratch holds no chunk", what);
+    }
+    return thermo_run(what, s, s->chunk, false, denom, n_denom, nn, out, n_products);
+}
+
 ipcr_status ipcr_thermo_legacy_products(const ipcr_scratch *s, const ipcr_genome *g, const double *denom, int64_t n_denom, double *out,
                                         int64_t n_products) {
-    if (!s || !g) return fail(IPCR_ERR_INVALID, "ipcr_thermo_legacy_products: null argument");
-    if (!s->products.empty() && s->last_was_chunk)
-        return fail(IPCR_ERR_INVALID, "ipcr_thermo_legacy_products: the last scan was an ipcr_scan_chunk: ipcr_thermo_legacy_scratch_products scores its products");
-    return thermo_run("ipcr_thermo_legacy_products", s, g, s->products_in_windows, denom, n_denom, out, n_products);
+    return thermo_products("ipcr_thermo_legacy_products", s, g, denom, n_denom, nullptr, out, n_products);
 }
 
 ipcr_status ipcr_thermo_legacy_scratch_products(const ipcr_scratch *s, const double *denom, int64_t n_denom, double *out, int64_t n_products) {
-    if (!s) return fail(IPCR_ERR_INVALID, "ipcr_thermo_legacy_scratch_products: null argument");
-    if (!s->stream) return fail(IPCR_ERR_DEVICE, "host-only scratch: the thermo score has no CPU fallback");
-    if (!s->last_was_chunk) return fail(IPCR_ERR_INVALID, "ipcr_thermo_legacy_scratch_products: the scratch's last scan was not an ipcr_scan_chunk");
-    if (!s->chunk) { // (an empty chunk, or an empty panel's chunk scan, which packs nothing)
-        if (s->products.empty() && n_products == 0) return IPCR_OK;
-        return fail(IPCR_ERR_INVALID, "ipcr_thermo_legacy_scratch_products: the scratch holds no chunk");
-    }
-    return thermo_run("ipcr_thermo_legacy_scratch_products", s, s->chunk, false, denom, n_denom, out, n_products);
+    return thermo_scratch_products("ipcr_thermo_legacy_scratch_products", s, denom, n_denom, nullptr, out, n_products);
+}
+
+ipcr_status ipcr_thermo_nn_duplex_products(const ipcr_scratch *s, const ipcr_genome *g, const ipcr_thermo_nn_primer *base, int64_t n_base,
+                                           double anneal_c, double *score, ipcr_thermo_nn_end *ends, int64_t n_products) {
+    const ThermoNN nn{base, n_base, anneal_c, ends};
+    return thermo_products("ipcr_thermo_nn_duplex_products", s, g, nullptr, 0, &nn, score, n_products);
+}
+
+ipcr_status ipcr_thermo_nn_duplex_scratch_products(const ipcr_scratch *s, const ipcr_thermo_nn_primer *base, int64_t n_base, double anneal_c,
+                                                   double *score, ipcr_thermo_nn_end *ends, int64_t n_products) {
+    const ThermoNN nn{base, n_base, anneal_c, ends};
+    return thermo_scratch_products("ipcr_thermo_nn_duplex_scratch_products", s, nullptr, 0, &nn, score, n_products);
 }
 
 // ipcr-nested on a worker: the products of the outer scratch's last ipcr_scan_chunk, their amplicons read from the tiles

@@ -6,6 +6,8 @@
 
 #include "device_types.h"
 
+struct ipcr_thermo_nn_end; // include/ipcr_hip.h
+
 namespace ipcr {
 hipError_t launch_pack(hipStream_t st, const uint8_t *seq, uint64_t len, uint64_t col0, uint64_t ncol,
                        uint32_t *planes, uint32_t *rst, uint64_t *colmask, uint32_t *rec_flags, uint64_t *rec_start_out = nullptr,
@@ -62,6 +64,12 @@ inline uint64_t launch_probe_tiles_max() { return 16384u; } // IPCR_PROBE_LDS_BY
 // caller has checked every window against its record and every primer index against the table
 hipError_t launch_thermo_legacy(hipStream_t st, const uint32_t *planes, const ipcr_thermo_end *ends, uint32_t nproducts,
                                 const ipcr_thermo_primer *primers, uint32_t nprimers, double *out);
+// nn-duplex-v1 thermo score (thermo_nn_kernels.hip): ends 2 i, 2 i + 1 = the two ends of product i -> score[i], and with
+// ends_out (may be null) ends_out[2 i], ends_out[2 i + 1]; the caller has checked every window and dangling position against
+// its record and every primer index against the table
+hipError_t launch_thermo_nn_duplex(hipStream_t st, const uint32_t *planes, const ipcr_thermo_nn_end_dev *ends, uint32_t nproducts,
+                                   const ipcr_thermo_nn_primer_dev *primers, uint32_t nprimers, double anneal_c, double *score,
+                                   ipcr_thermo_nn_end *ends_out);
 // header lines ('>' at a line start .. its line end) of a raw FASTA slab, unordered; *count may exceed cap
 hipError_t launch_fasta_find_headers(hipStream_t st, const uint8_t *raw, uint64_t n, uint32_t at_line_start, ipcr_fasta_range *list,
                                      uint32_t cap, uint32_t *count);

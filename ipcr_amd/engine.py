@@ -300,6 +300,26 @@ class SimulationScratch:
             _lib.check(_lib.lib().ipcr_thermo_legacy_products(self._h, genome._h, d, nd, out, n))
         return out[:n]
 
+    def thermo_nn_scores(self, genome: Optional["Genome"] = None, base: Sequence = (), anneal_c: float = 60.0, details: bool = False):
+        """Score of every product of the last scan on this scratch under `--thermo-model nn-duplex-v1`
+        (internal/thermovisitors/score.go:637-690): the smaller anneal margin of its two ends, NaN for a product the model
+        does not score.  Computed on the device from the tiles, as thermo_scores: the resident `genome`
+        (ipcr_thermo_nn_duplex_products), or -- without one -- the chunk of the last ipcr_scan_chunk
+        (ipcr_thermo_nn_duplex_scratch_products).  `base`: (tm_c, denom) of pair p's forward / reverse primer at 2 p /
+        2 p + 1 (thermo.panel_nn_base).  details: -> (scores, ends), ends[i] = the (left, right) _lib.ThermoNNEnd of product i."""
+        n = self.num_products()
+        out = (C.c_double * max(n, 1))()
+        nb = len(base)
+        b = (_lib.ThermoNNPrimer * max(nb, 1))(*(_lib.ThermoNNPrimer(float(t), float(d)) for t, d in base))
+        ends = (_lib.ThermoNNEnd * max(2 * n, 1))() if details else None
+        if genome is None:
+            _lib.check(_lib.lib().ipcr_thermo_nn_duplex_scratch_products(self._h, b, nb, float(anneal_c), out, ends, n))
+        else:
+            _lib.check(_lib.lib().ipcr_thermo_nn_duplex_products(self._h, genome._h, b, nb, float(anneal_c), out, ends, n))
+        if not details:
+            return out[:n]
+        return out[:n], [(ends[2 * i], ends[2 * i + 1]) for i in range(n)]
+
 
 def _fill_sites(pr: Product, seq: bytes) -> None:
     """FwdSite / RevSite as core/engine/engine.go:175-183 slices them (NeedSites, pretty text only):

@@ -132,6 +132,11 @@ class Batch:
         thermo.panel_denoms (--denom auto), None for 200.0."""
         return self.sc.thermo_scores(self.genome, denoms)
 
+    def thermo_nn_scores(self, base, anneal_c: float, details: bool = False):
+        """the nn-duplex-v1 Score of every product (score.go:637-690), computed on the device from the same tiles.  `base`:
+        thermo.panel_nn_base; details: -> (scores, ends) as engine.SimulationScratch.thermo_nn_scores"""
+        return self.sc.thermo_nn_scores(self.genome, base, anneal_c, details)
+
     def probe_hits(self, probe: str, max_mm: int):
         """ipcr-probe keeps --chunk-size (internal/probeapp/app.go:108): every product is annotated from its own
         amplicon, rescanned from the tiles it was found in (pipeline.go:80-89 slices Product.Seq chunk-locally too)"""

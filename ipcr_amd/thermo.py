@@ -2,8 +2,10 @@
 auto`, the score ordering and Go's float formats.  The score itself is computed by the library: per product on the device
 (ipcr_thermo_legacy_products), per end on the host (ipcr_thermo_legacy_penalty).
 
-Restates core/thermo/conditions.go, core/thermo/nn.go:94-276, internal/thermovisitors/score.go:95-110 and :465-492, and
-internal/common/sort.go:81-95.  The NN models (nn-duplex-v1, nn-structure-v1) are not built.
+Restates core/thermo/conditions.go, core/thermo/nn.go:94-301, internal/thermovisitors/score.go:95-110 and :465-492, and
+internal/common/sort.go:81-95.  Of the NN models nn-duplex-v1 is built as a library feature: PerfectDuplex and panel_nn_base
+give the per-primer base that ipcr_thermo_nn_duplex_products takes (engine.SimulationScratch.thermo_nn_scores); the driver
+still refuses the model (UNBUILT_MODELS), and nn-structure-v1 is not built.
 """
 from __future__ import annotations
 
@@ -273,6 +275,72 @@ def panel_denoms(pairs: Sequence, cond: Optional[Conditions]) -> Optional[list]:
             if seq not in cache:
                 cache[seq] = denom_for_primer(seq, cond)
             out.append(cache[seq])
+    return out
+
+
+@dataclass
+class DuplexResult:
+    """thermo.DuplexResult -- nn.go:81-88, the fields PerfectDuplex fills beside the Tm result"""
+    Result: TmResult
+    TmC: float
+    AnnealC: float
+    AnnealMarginC: float
+    DeltaGAtAnnealKcal: float
+    EffectiveDenomCalK: float
+    SelfComplementary: bool
+
+
+def PerfectDuplex(primer5to3: str, cond: Conditions) -> DuplexResult:
+    """thermo.PerfectDuplex -- nn.go:279-301, of a primer on its own complement (what ImperfectDuplex anchors on,
+    imperfect.go:264-268).  ValueError where the reference returns an error."""
+    p = primer5to3.strip().upper()
+    if not p or any(ch not in _COMP for ch in p):
+        raise ValueError("PerfectDuplex: non-ACGT base in primer")
+    comp = "".join(_COMP[ch] for ch in p)
+    c = cond.WithDefaults()
+    c.SelfComplementary = comp[::-1] == p
+    inp = c.TmInput()
+    res = Tm(p, comp, inp)
+    denom = res.DS_Na + RCAL * math.log(inp.CT / float(inp.X))
+    dg = res.DH_kcal - (c.AnnealC + 273.15) * denom / 1000.0
+    return DuplexResult(res, res.TmC, c.AnnealC, res.TmC - c.AnnealC, dg, denom, c.SelfComplementary)
+
+
+def nn_base_for_primer(primer5to3: str, cond: Conditions):
+    """(tm_c, denom) of one primer for ipcr_thermo_nn_duplex_*: TmC and |EffectiveDenomCalK| of its perfect duplex, the
+    denominator 200.0 when that is NaN, +-Inf or 0 (imperfect.go:273-276).  A primer that is not pure ACGT -- or whose Tm
+    cannot be computed, where the reference returns an error for every product of it -- gets a finite placeholder: the
+    library gives its ends status 1 in the first case; the second cannot arise from conditions score_conditions accepts."""
+    try:
+        d = PerfectDuplex(primer5to3, cond)
+    except (ValueError, ZeroDivisionError, OverflowError):
+        return 0.0, FIXED_DENOM
+    denom = abs(d.EffectiveDenomCalK)
+    if math.isnan(denom) or math.isinf(denom) or denom == 0:
+        denom = FIXED_DENOM
+    return (d.TmC if math.isfinite(d.TmC) else 0.0), denom
+
+
+def panel_nn_base(pairs: Sequence, cond: Conditions) -> list:
+    """the table ipcr_thermo_nn_duplex_products takes: (tm_c, denom) of pair p's forward / reverse primer at 2 p / 2 p + 1,
+    under Score.conditions() (score_conditions) of `cond`; the anneal temperature that goes with it is
+    score_conditions(cond).AnnealC"""
+    c = score_conditions(cond)
+    cache, out = {}, []
+    for pr in pairs:
+        for seq in (pr.Forward, pr.Reverse):
+            if seq not in cache:
+                cache[seq] = nn_base_for_primer(seq, c)
+            out.append(cache[seq])
+    return out
+
+
+def nn_duplex_end(primer5to3: str, target3to5: str, dangling3p: str, tm_c: float, denom: float) -> "_lib.ThermoNNEnd":
+    """ipcr_thermo_nn_duplex_end: one end on the host; dangling3p: the template base next to the primer's 3' end, "" for none"""
+    out = _lib.ThermoNNEnd()
+    d = dangling3p.encode("latin-1") if dangling3p else b"\0"
+    _lib.check(_lib.lib().ipcr_thermo_nn_duplex_end(primer5to3.encode("latin-1"), target3to5.encode("latin-1"), d, float(tm_c),
+                                                    float(denom), C.byref(out)))
     return out
 
 
